@@ -2,6 +2,7 @@
 """bench.py -- rows/sec of the h2o group-by hot path on MI355X, against the HBM roofline.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                 (also writes the last step's result arrays as DIR/*.npy)
 
 Workload (BASELINE.json metric "rows/sec on h2o groupby 1e9-row"): h2o Q1
 `SELECT id1, sum(v1) FROM source GROUP BY id1` (reference benchmark/h2o/groupby.sql:1) on 1e9 synthetic
@@ -201,6 +202,17 @@ def secondary_entries(dev, n, ck, aq, id1, v1):
     return out
 
 
+def dump_outputs(out_dir, final, ck, join):
+    """The arrays a caller of the timed call receives from its last step: the group keys (id1) and the per-group sums, both in the
+    library's group order (first occurrence), as float64 .npy files.  100 groups: a few KB in all.  The sums are 128-bit integers
+    on the device; they are exact in float64 at the sizes bench.py runs (|sum| < 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    keys = final.keys(0, np.int32).astype(np.float64)
+    sums = np.array([float(x) for x in ck.i128_to_int(final.result(0, ck.RED_SUM, ck.INT64 if join else ck.INT32))], dtype=np.float64)
+    np.save(os.path.join(out_dir, "group_keys_id1.npy"), keys)
+    np.save(os.path.join(out_dir, "sum_v1_times_w.npy" if join else "sum_v1.npy"), sums)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -212,7 +224,12 @@ def main():
     ap.add_argument("--workload", choices=["q1", "join"], default="q1",
                     help="q1 (default, the graded metric): sum(v1) by id1.  join: BASELINE config 4, fact JOIN small(id4, w) ON id4, "
                          "sum(v1 * w) by id1 through the fused aqg_join_groupby_sum, same shard merge")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (the group keys and the per-group sums, in the "
+                         "library's group order) as DIR/<name>.npy in float64, on rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -380,6 +397,9 @@ def main():
         local_sum = int(t.item())
     assert total == local_sum, (total, local_sum)
     assert final.ngroups == 100
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final, ck, join)
 
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps

@@ -18,9 +18,12 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def ref():
+def ref_answers():
+    """the real reference's answers: live where oracle/_ref is built, recorded digests everywhere (tests/golden_util.py)"""
     import checker
-    r = checker.load_ref()
-    if r is None:
-        pytest.skip("oracle/_ref/libaqref.so not built (reference tree not mounted)")
-    return r
+    import golden_util
+    ra = golden_util.RefAnswers(checker.load_ref(), record=os.environ.get("AQG_RECORD_REF_DIGESTS") == "1")
+    yield ra
+    if ra.record:
+        ra.save()
+

@@ -396,6 +396,19 @@ def test_bench_self_merge_world_of_one():
     assert line["n_gpus"] == 1 and line["config"]["groups"] == 100 and "secondary" not in line
 
 
+def test_bench_dump_outputs_are_the_oracle_groups(tmp_path, oracle):
+    """`bench.py --dump-outputs DIR`: the last timed step's keys and sums, in group order, equal to the oracle's on the same seeded rows"""
+    n = 3_000_000
+    line = _bench(["--rows", "3e6", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--no-secondary", "--dump-outputs", str(tmp_path)], {})
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    keys, sums = np.load(tmp_path / "group_keys_id1.npy"), np.load(tmp_path / "sum_v1.npy")
+    assert keys.dtype == sums.dtype == np.float64 and keys.shape == sums.shape == (100,)
+    hid1, hv1 = oracle.gen_column(ck.GEN_ID1, 42, 0, n, n, 100), oracle.gen_column(ck.GEN_V1, 42, 0, n, n, 100)
+    ogb = oracle.groupby([hid1])
+    assert np.array_equal(keys, hid1[ogb["first_rows"]].astype(np.float64))
+    assert np.array_equal(sums, np.array([float(x) for x in ck.i128_to_int(oracle.grouped_reduce(ck.RED_SUM, hv1, ogb))]))
+
+
 def test_rccl_transport_after_torch_has_loaded_its_own_rocm_stack():
     """bench.py --gpus N imports torch (whose wheel bundles libamdhip64 / libhsa-runtime64 / librccl) BEFORE the library makes its
     communicator: the library must open the RCCL that sits next to the HIP runtime it is bound to (a fresh process, torch first)"""

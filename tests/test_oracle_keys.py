@@ -1,6 +1,7 @@
 """Group-by over key columns that are not plain integers (reference server/hasher.h:97-144 + tuple ==): the oracle's restatement
 of the equality rules against golden ids dumped from the REAL reference (tests/golden/ref_golden_keys.json, made by
-oracle/gen_golden_keys.py over the seeded inputs of tests/keycases.py), and against the reference itself where it is built."""
+oracle/gen_golden_keys.py over the seeded inputs of tests/keycases.py), and against the reference's recorded answers
+(tests/golden/ref_digests.json), asked live as well where it is built."""
 import json
 import os
 
@@ -34,15 +35,14 @@ def test_quirks_pinned_by_the_reference(oracle):
     assert g["ngroups"] > 30          # the NaN rows of the seeded case each made a group
 
 
-def test_oracle_vs_real_reference_where_built(oracle, ref):
-    if ref is None:
-        import pytest
-        pytest.skip("oracle/_ref not built here")
+def test_oracle_vs_real_reference(oracle, ref_answers):
+    R = ref_answers.check
     for name, cols in keycases.cases():
-        a, b = oracle.groupby_typed(cols), ref.groupby_typed(cols)
-        assert a["ngroups"] == b["ngroups"] and np.array_equal(a["reversemap"], b["reversemap"]) and np.array_equal(a["first_rows"], b["first_rows"]), name
+        a = oracle.groupby_typed(cols)
+        for f in ("ngroups", "reversemap", "first_rows"):
+            R(f"keys/{name}/{f}", a[f], lambda r: r.groupby_typed(cols)[f])
     # raw string pointers are POINTERS under the reference's tuple == (mem_opt.cpp:22 groups by ColRef<const char*>)
     import ctypes as C
     bufs = [C.create_string_buffer(b) for b in (b"abc", b"abc", b"abd")]
     ptrs = np.array([C.addressof(bufs[0]), C.addressof(bufs[1]), C.addressof(bufs[2]), C.addressof(bufs[0])], np.uint64)
-    assert ref.groupby_typed([(ck.UINT64, ptrs)])["reversemap"].tolist() == [0, 1, 2, 0]
+    R("keys/raw_string_pointers/reversemap", np.array([0, 1, 2, 0], np.uint32), lambda r: r.groupby_typed([(ck.UINT64, ptrs)])["reversemap"])

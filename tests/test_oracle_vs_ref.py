@@ -1,6 +1,6 @@
-"""Pins the C restatement (oracle/aq_oracle.c) against the REAL reference library
-(oracle/_ref/libaqref.so, built from /root/reference by oracle/Makefile) on seeded
-random inputs, bit for bit.  Skipped where the reference build is absent."""
+"""Pins the C restatement (oracle/aq_oracle.c) against the REAL reference library on seeded random inputs, bit for bit: against
+the digests of its answers recorded in tests/golden/ref_digests.json (oracle/gen_ref_digests.py) everywhere, and against the library
+itself (oracle/_ref/libaqref.so, built by oracle/Makefile) where it is built."""
 import numpy as np
 import pytest
 
@@ -19,39 +19,40 @@ def rand(rng, dt, n, small=False):
     return rng.integers(lo, hi, n, endpoint=True).astype(dt)
 
 
-def same(a, b):
-    return a.dtype == b.dtype and a.tobytes() == b.tobytes()
+def nm(dt):
+    return np.dtype(dt).name
 
 
 @pytest.mark.parametrize("dt", NUM_DTYPES)
-def test_type_rules(oracle, ref, dt):
+def test_type_rules(oracle, ref_answers, dt):
+    R = ref_answers.check
     t = ck.NP2TAG[np.dtype(dt)]
-    assert oracle.long_type(t) == ref.long_type(t)
-    assert oracle.fp_type(t) == ref.fp_type(t)
+    k = f"type_rules/{nm(dt)}"
+    R(f"{k}/long_type", oracle.long_type(t), lambda r: r.long_type(t))
+    R(f"{k}/fp_type", oracle.fp_type(t), lambda r: r.fp_type(t))
     for dt2 in NUM_DTYPES:
         t2 = ck.NP2TAG[np.dtype(dt2)]
-        assert oracle.coercion(t, t2) == ref.coercion(t, t2), (dt, dt2)
+        R(f"{k}/coercion/{nm(dt2)}", oracle.coercion(t, t2), lambda r: r.coercion(t, t2))
     for op in range(9):
-        assert oracle.reduce_out_dtype(op, t) == ref.reduce_out_dtype(op, t)
+        R(f"{k}/reduce_out/{op}", oracle.reduce_out_dtype(op, t), lambda r: r.reduce_out_dtype(op, t))
     for op in range(12):
-        assert oracle.scan_out_dtype(op, t) == ref.scan_out_dtype(op, t)
+        R(f"{k}/scan_out/{op}", oracle.scan_out_dtype(op, t), lambda r: r.scan_out_dtype(op, t))
 
 
 @pytest.mark.parametrize("dt", NUM_DTYPES)
 @pytest.mark.parametrize("n", [0, 1, 2, 7, 1000])
-def test_reduce(oracle, ref, dt, n):
+def test_reduce(oracle, ref_answers, dt, n):
     rng = np.random.default_rng(n * 31 + np.dtype(dt).num)
     x = rand(rng, dt, n)
     for name, op in ck.RED_NAMES.items():
         if n == 0 and name in ("avg",):
             continue  # 0/0 = NaN on both sides
-        a, b = oracle.reduce(op, x), ref.reduce(op, x)
-        assert np.array(a).tobytes() == np.array(b).tobytes(), (name, a, b)
+        ref_answers.check(f"reduce/{nm(dt)}/{n}/{name}", oracle.reduce(op, x), lambda r: r.reduce(op, x))
 
 
 @pytest.mark.parametrize("dt", NUM_DTYPES)
 @pytest.mark.parametrize("n", [0, 1, 5, 257])
-def test_scan(oracle, ref, dt, n):
+def test_scan(oracle, ref_answers, dt, n):
     rng = np.random.default_rng(n * 17 + np.dtype(dt).num)
     x = rand(rng, dt, n)
     x[x == 0] = 1
@@ -61,13 +62,13 @@ def test_scan(oracle, ref, dt, n):
         for w in (0, 1, 2, 3, 10, 256, 257, 1000):
             if w == 0 and name in ("ratiow", "sumw", "avgw"):
                 continue  # undefined in the reference (reads ret[-1] / divides by zero)
-            a, b = oracle.scan(op, x, w), ref.scan(op, x, w)
-            assert same(a, b), (name, w, dt)
+            ref_answers.check(f"scan/{nm(dt)}/{n}/{name}/{w}", oracle.scan(op, x, w), lambda r: r.scan(op, x, w))
 
 
 @pytest.mark.parametrize("lt", BIN_DTYPES)
 @pytest.mark.parametrize("rt", BIN_DTYPES)
-def test_ewise_free_ops(oracle, ref, lt, rt):
+def test_ewise_free_ops(oracle, ref_answers, lt, rt):
+    R = ref_answers.check
     rng = np.random.default_rng(np.dtype(lt).num * 100 + np.dtype(rt).num)
     n = 301
     l, r = rand(rng, lt, n), rand(rng, rt, n)
@@ -75,66 +76,72 @@ def test_ewise_free_ops(oracle, ref, lt, rt):
     l[l == 0] = 5
     tl, tr = ck.NP2TAG[np.dtype(lt)], ck.NP2TAG[np.dtype(rt)]
     for op in (ck.OP_ADD, ck.OP_SUB, ck.OP_MUL, ck.OP_DIV, ck.OP_GT):
-        assert oracle.ewise_out_dtype(op, tl, tr) == ref.ewise_out_dtype(op, tl, tr), (op, lt, rt)
-        assert same(oracle.ewise(op, l, r), ref.ewise(op, l, r)), (op, lt, rt, "vv")
-        assert same(oracle.ewise(op, l, r[7]), ref.ewise(op, l, r[7])), (op, lt, rt, "vs")
-        assert same(oracle.ewise(op, l[9], r), ref.ewise(op, l[9], r)), (op, lt, rt, "sv")
+        k = f"ewise/{nm(lt)}/{nm(rt)}/{op}"
+        R(f"{k}/out", oracle.ewise_out_dtype(op, tl, tr), lambda ref: ref.ewise_out_dtype(op, tl, tr))
+        R(f"{k}/vv", oracle.ewise(op, l, r), lambda ref: ref.ewise(op, l, r))
+        R(f"{k}/vs", oracle.ewise(op, l, r[7]), lambda ref: ref.ewise(op, l, r[7]))
+        R(f"{k}/sv", oracle.ewise(op, l[9], r), lambda ref: ref.ewise(op, l[9], r))
 
 
 @pytest.mark.parametrize("lt", BIN_DTYPES)
 @pytest.mark.parametrize("rt", BIN_DTYPES)
-def test_ewise_aqop(oracle, ref, lt, rt):
+def test_ewise_aqop(oracle, ref_answers, lt, rt):
+    R = ref_answers.check
     rng = np.random.default_rng(np.dtype(lt).num * 7 + np.dtype(rt).num)
     n = 130
     l, r = rand(rng, lt, n, small=True), rand(rng, rt, n, small=True)
     for op in (ck.OP_LT, ck.OP_GE, ck.OP_LE, ck.OP_EQ, ck.OP_NE):
-        assert same(oracle.ewise(op, l, r, ot=ck.BOOL), ref.ewise(op, l, r, ot=ck.BOOL)), (op, lt, rt)
+        R(f"aqop/{nm(lt)}/{nm(rt)}/{op}", oracle.ewise(op, l, r, ot=ck.BOOL), lambda ref: ref.ewise(op, l, r, ot=ck.BOOL))
     if np.dtype(lt).kind != "f" and np.dtype(rt).kind != "f":
         for op in (ck.OP_AND, ck.OP_OR, ck.OP_XOR):
-            assert same(oracle.ewise(op, l, r, ot=ck.INT32), ref.ewise(op, l, r, ot=ck.INT32)), (op, lt, rt)
+            R(f"aqop/{nm(lt)}/{nm(rt)}/{op}", oracle.ewise(op, l, r, ot=ck.INT32), lambda ref: ref.ewise(op, l, r, ot=ck.INT32))
 
 
 @pytest.mark.parametrize("dt", [np.int32, np.int64, np.float32, np.float64, np.uint8])
-def test_unary(oracle, ref, dt):
+def test_unary(oracle, ref_answers, dt):
+    R = ref_answers.check
     rng = np.random.default_rng(5)
     x = np.abs(rand(rng, dt, 100))
-    assert same(oracle.unary(ck.UN_SQRT, x), ref.unary(ck.UN_SQRT, x))
+    R(f"unary/{nm(dt)}/sqrt", oracle.unary(ck.UN_SQRT, x), lambda r: r.unary(ck.UN_SQRT, x))
     if np.dtype(dt).kind == "f":
         for p in (0, 2, 6, 7, 20):
-            assert same(oracle.unary(ck.UN_TRUNCATE, x, p), ref.unary(ck.UN_TRUNCATE, x, p)), p
+            R(f"unary/{nm(dt)}/truncate/{p}", oracle.unary(ck.UN_TRUNCATE, x, p), lambda r: r.unary(ck.UN_TRUNCATE, x, p))
 
 
 @pytest.mark.parametrize("lt", BIN_DTYPES)
 @pytest.mark.parametrize("rt", BIN_DTYPES)
-def test_corr(oracle, ref, lt, rt):
+def test_corr(oracle, ref_answers, lt, rt):
     rng = np.random.default_rng(11)
     x, y = rand(rng, lt, 500, small=True), rand(rng, rt, 500, small=True)
-    a, b = oracle.corr(x, y), ref.corr(x, y)
-    assert np.float64(a).tobytes() == np.float64(b).tobytes(), (a, b)
+    ref_answers.check(f"corr/{nm(lt)}/{nm(rt)}", np.float64(oracle.corr(x, y)), lambda r: np.float64(r.corr(x, y)))
 
 
 @pytest.mark.parametrize("dt", NUM_DTYPES)
-def test_gather_compact(oracle, ref, dt):
+def test_gather_compact(oracle, ref_answers, dt):
+    R = ref_answers.check
     rng = np.random.default_rng(3)
     x = rand(rng, dt, 400)
     idx = rng.integers(0, 400, 1000).astype(np.uint32)
-    assert same(oracle.gather(x, idx), ref.gather(x, idx))
+    R(f"gather/{nm(dt)}", oracle.gather(x, idx), lambda r: r.gather(x, idx))
     mask = rng.integers(0, 2, 400).astype(np.uint8)
-    assert same(oracle.compact(x, mask), ref.compact(x, mask))
+    R(f"compact/{nm(dt)}", oracle.compact(x, mask), lambda r: r.compact(x, mask))
     assert oracle.compact(x, np.zeros(400, np.uint8)).size == 0
 
 
-def test_hash_kats(oracle, ref):
+def test_hash_kats(oracle, ref_answers):
+    R = ref_answers.check
     # SURVEY 8c a16
-    assert oracle.hash_scalar(np.int32(7)) == ref.hash_scalar(np.int32(7)) == 6018027440424182935
-    assert oracle.hash_tuple([np.int32(3), np.int32(4)]) == ref.hash_tuple([np.int32(3), np.int32(4)]) == 11708105269577805707
+    assert oracle.hash_scalar(np.int32(7)) == 6018027440424182935
+    assert oracle.hash_tuple([np.int32(3), np.int32(4)]) == 11708105269577805707
+    R("hash/kat_scalar_7", oracle.hash_scalar(np.int32(7)), lambda r: r.hash_scalar(np.int32(7)))
+    R("hash/kat_tuple_3_4", oracle.hash_tuple([np.int32(3), np.int32(4)]), lambda r: r.hash_tuple([np.int32(3), np.int32(4)]))
     rng = np.random.default_rng(1)
-    for v in rng.integers(-2**31, 2**31 - 1, 50):
-        assert oracle.hash_scalar(np.int32(v)) == ref.hash_scalar(np.int32(v))
-    for _ in range(20):
+    for i, v in enumerate(rng.integers(-2**31, 2**31 - 1, 50)):
+        R(f"hash/scalar/{i}", oracle.hash_scalar(np.int32(v)), lambda r: r.hash_scalar(np.int32(v)))
+    for i in range(20):
         vals = [np.int32(v) for v in rng.integers(-1000, 1000, 6)]
         for k in (1, 2, 3, 6):
-            assert oracle.hash_tuple(vals[:k]) == ref.hash_tuple(vals[:k])
+            R(f"hash/tuple/{i}/{k}", oracle.hash_tuple(vals[:k]), lambda r: r.hash_tuple(vals[:k]))
 
 
 GB_CASES = [
@@ -143,23 +150,25 @@ GB_CASES = [
 
 
 @pytest.mark.parametrize("nk,n,card", GB_CASES)
-def test_groupby(oracle, ref, nk, n, card):
+def test_groupby(oracle, ref_answers, nk, n, card):
+    R = ref_answers.check
     rng = np.random.default_rng(nk * 1000 + n + card)
     keys = [rng.integers(-card, card, n).astype(np.int32) for _ in range(nk)]
-    a, b = oracle.groupby(keys), ref.groupby(keys)
-    assert a["ngroups"] == b["ngroups"]
+    a = oracle.groupby(keys)
+    k = f"groupby/{nk}/{n}/{card}"
+    R(f"{k}/ngroups", a["ngroups"], lambda r: r.groupby(keys)["ngroups"])
     for f in ("reversemap", "counts", "first_rows", "offsets", "row_ids"):
-        assert np.array_equal(a[f], b[f]), f
+        R(f"{k}/{f}", a[f], lambda r: r.groupby(keys)[f])
     for vdt in (np.int32, np.float32, np.int64, np.float64):
         v = rand(rng, vdt, n, small=True)
         for name in ("sum", "min", "max", "count", "avg", "first", "last", "var"):
-            x, y = oracle.grouped_reduce(ck.RED_NAMES[name], v, a), ref.grouped_reduce(ck.RED_NAMES[name], v, b)
-            assert same(x, y), (name, vdt)
+            op = ck.RED_NAMES[name]
+            R(f"{k}/{nm(vdt)}/{name}", oracle.grouped_reduce(op, v, a), lambda r: r.grouped_reduce(op, v, r.groupby(keys)))
 
 
-def test_groupby_int64_key(oracle, ref):
+def test_groupby_int64_key(oracle, ref_answers):
     rng = np.random.default_rng(8)
     k = (rng.integers(0, 50, 2000).astype(np.int64) << 33) - 7
-    a, b = oracle.groupby([k]), ref.groupby([k])
+    a = oracle.groupby([k])
     for f in ("reversemap", "counts", "first_rows", "offsets", "row_ids"):
-        assert np.array_equal(a[f], b[f]), f
+        ref_answers.check(f"groupby_int64_key/{f}", a[f], lambda r: r.groupby([k])[f])
