@@ -1,6 +1,6 @@
 // scan.hip -- prefix scans, sliding windows and shifts of a column
 // (reference server/aggregations.h: mins/maxs :89-125, minw/maxw :127-167, ratiow :169-201,
-//  sums/avgs :203-236, sumw/avgw :238-281, vars/stddevs :350-381, varw/stddevw :283-330,
+//  sums/avgs :203-236, sumw/avgw :238-281, vars/stddevs :350-381, varw/stddevw :283-330 (D9),
 //  deltas/prev/aggnext :439-485).
 //
 // Prefix scans: reduce-then-scan over 2048-element tiles (tile reduce -> one-workgroup scan of the
@@ -8,6 +8,8 @@
 // wavefront inclusive scan (__shfl_up over 64 lanes), LDS combine of the 4 waves.
 // Windows: every tile stages its elements plus a (w-1)-element halo in LDS; sums use the tile-local
 // prefix difference S[i]-S[i-w] (exact for integers), min/max use log2(w) LDS doubling steps.
+// Variances work on differences from an anchor taken from the data (mom_alg, scan_dev.hpp): short windows by two passes over the
+// window, running variances and longer windows from prefix moments about the first element.
 // Integer results are exact (bit-identical to the reference); floating sums follow a tree order.
 // HBM-bound; algorithmic bytes per row = sizeof(T) + sizeof(out).
 #include "aqg_internal.hpp"
@@ -239,24 +241,22 @@ __global__ void __launch_bounds__(SB) shift_kernel(const T* __restrict__ x, uint
 }
 
 // ---- sliding sums: tile + halo in LDS, prefix difference -------------------------------------------
-// MODE 0 sumw (LongType out) / 1 avgw (double) / 2 varw / 3 stddevw (intended population variance; see D9)
+// MODE 0 sumw (LongType out) / 1 avgw (double)
 template <class T, int MODE>
 __global__ void __launch_bounds__(SB) window_sum_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, void* __restrict__ out) {
-    using ALG = std::conditional_t<(MODE >= 2), dsum_alg<T>, sum_alg<T>>;
+    using ALG = sum_alg<T>;
     using A = typename ALG::A;
     extern __shared__ __align__(16) unsigned char smem_raw[];
     __shared__ A lds_w[8];
-    __shared__ A lds_w2[8];
     const uint32_t tile_start = blockIdx.x * TS, tile_end = tile_start + TS < n ? tile_start + TS : n;
     // LDS position p <-> row tile_start - H + p, with the halo H = w - 1 rounded up to whole blocks of IT rows; rows before
     // row 0 count as zeros, so the growing prefix of the first w rows needs no special case below
     const uint32_t H = (w - 1 + IT - 1) / IT * IT;
     const uint32_t L = H + TS, nblk = L / IT;
     A* S = reinterpret_cast<A*>(smem_raw);                       // inclusive prefix of x over the extended tile
-    A* Q = S + (MODE >= 2 ? L : 0);                              // inclusive prefix of x*x (variance modes)
     // a lane takes blocks of IT consecutive rows straight from HBM (vector load), scans them in registers and writes the
     // prefixes to LDS once; blocks beyond the first SB (the halo's worth) take further rounds with a running carry
-    A carry = ALG::identity(), carry2 = ALG::identity();
+    A carry = ALG::identity();
     for (uint32_t blk0 = 0; blk0 < nblk; blk0 += SB) {
         const uint32_t blk = blk0 + threadIdx.x;
         const int64_t g0 = (int64_t)tile_start - (int64_t)H + (int64_t)blk * IT;
@@ -269,23 +269,17 @@ __global__ void __launch_bounds__(SB) window_sum_kernel(const T* __restrict__ x,
 #pragma unroll
             for (int j = 0; j < IT; ++j) { const int64_t g = g0 + j; v[j] = (blk < nblk && g >= 0 && g < (int64_t)n) ? x[g] : (T)0; }
         }
-        A loc[IT], loc2[IT];
-        A a = ALG::identity(), q = ALG::identity();
+        A loc[IT];
+        A a = ALG::identity();
 #pragma unroll
-        for (int j = 0; j < IT; ++j) {
-            a = ALG::op(a, ALG::lift(v[j])); loc[j] = a;
-            if constexpr (MODE >= 2) { q = q + (double)v[j] * (double)v[j]; loc2[j] = q; }
-        }
-        A tot, tot2;
+        for (int j = 0; j < IT; ++j) { a = ALG::op(a, ALG::lift(v[j])); loc[j] = a; }
+        A tot;
         A excl = ALG::op(carry, block_scan_excl<ALG>(a, lds_w, tot));
-        A excl2 = ALG::identity();
-        if constexpr (MODE >= 2) excl2 = ALG::op(carry2, block_scan_excl<ALG>(q, lds_w2, tot2));
         if (blk < nblk) {
 #pragma unroll
-            for (int j = 0; j < IT; ++j) { S[blk * IT + j] = ALG::op(excl, loc[j]); if constexpr (MODE >= 2) Q[blk * IT + j] = ALG::op(excl2, loc2[j]); }
+            for (int j = 0; j < IT; ++j) S[blk * IT + j] = ALG::op(excl, loc[j]);
         }
         carry = ALG::op(carry, tot);
-        if constexpr (MODE >= 2) carry2 = ALG::op(carry2, tot2);
     }
     __syncthreads();
     for (uint32_t i = tile_start + threadIdx.x; i < tile_end; i += SB) {
@@ -295,14 +289,8 @@ __global__ void __launch_bounds__(SB) window_sum_kernel(const T* __restrict__ x,
         if constexpr (MODE == 0) {
             if constexpr (std::is_floating_point_v<T>) static_cast<double*>(out)[i] = s;
             else static_cast<aqg_i128*>(out)[i] = ALG::to_i128(s);
-        } else if constexpr (MODE == 1) {
-            static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
         } else {
-            A sq = idx >= len ? ALG::sub(Q[idx], Q[idx - len]) : Q[idx];
-            double m = ALG::to_double(s) / (double)len;
-            double var = ALG::to_double(sq) / (double)len - m * m;
-            if (var < 0) var = 0;
-            static_cast<double*>(out)[i] = MODE == 3 ? sqrt(var) : var;
+            static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
         }
     }
 }
@@ -614,31 +602,56 @@ __global__ void __launch_bounds__(SB) tile_scan_raw_kernel(const T* __restrict__
     for (uint32_t j = 0; j < cnt; ++j) { run = ALG::op(run, ALG::lift(v[j])); out[base + j] = run; }
 }
 
-// running variance (vars / stddevs): MnX_i = ssq_i - s_i^2/(i+1), value = MnX_i/(i+1) -- from exact prefix sums of
-// x and x*x (the reference updates MnX with a floating recurrence, aggregations.h:364-372)
-template <class T, bool SD>
-__global__ void __launch_bounds__(SB) vars_kernel(const T* __restrict__ x, uint32_t n, const double* __restrict__ tp_s, const double* __restrict__ tp_q,
-                                                  double* __restrict__ out) {
-    using dalg = dsum_alg<T>;
-    __shared__ double lds_w[8];
-    __shared__ double lds_w2[8];
+// running variance (vars / stddevs, WR 0 / 1) from the moments about x[0] (mom_alg of scan_dev.hpp) of every prefix: the tile's
+// carry-in from the tile aggregates' scan, then the lane's elements; WR 2 writes the prefix moments themselves (windows longer than
+// VAR_DIRECT_MAX_W: var_prefix_diff_kernel).  The reference updates MnX with a floating recurrence (aggregations.h:364-372).
+template <class T, int WR>
+__global__ void __launch_bounds__(SB) var_scan_kernel(const T* __restrict__ x, uint32_t n, const typename mom_alg<T>::A* __restrict__ tile_prefix, void* __restrict__ out) {
+    using ALG = mom_alg<T>;
+    using A = typename ALG::A;
+    using O = std::conditional_t<WR == 2, dpair, double>;
+    __shared__ A lds_w[8];
+    extern __shared__ __align__(16) unsigned char stage_raw[];
     uint32_t base = blockIdx.x * TS + threadIdx.x * IT, cnt;
     T v[IT];
     load_tile_items(x, n, base, v, cnt);
-    double a = 0, q = 0;
+    A a = ALG::identity();
 #pragma unroll
-    for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) { double d = (double)v[j]; a += d; q += d * d; }
-    double t1, t2;
-    double rs = tp_s[blockIdx.x] + block_scan_excl<dalg>(a, lds_w, t1);
-    double rq = tp_q[blockIdx.x] + block_scan_excl<dalg>(q, lds_w2, t2);
-    for (uint32_t j = 0; j < cnt; ++j) {
-        double d = (double)v[j];
-        rs += d; rq += d * d;
-        double cntd = (double)(base + j + 1);
-        double var = (rq - rs * rs / cntd) / cntd;
-        if (var < 0) var = 0;
-        out[base + j] = SD ? sqrt(var) : var;
+    for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) a = ALG::op(a, ALG::lift(v[j]));
+    A total;
+    A run = ALG::op(tile_prefix[blockIdx.x], block_scan_excl<ALG>(a, lds_w, total));
+    O o[IT];
+#pragma unroll
+    for (int j = 0; j < IT; ++j) {
+        if ((uint32_t)j < cnt) run = ALG::op(run, ALG::lift(v[j]));
+        if constexpr (WR == 2) o[j] = dpair{run.s, run.q};
+        else { const double var = var_from(run.s, run.q, (double)run.n); o[j] = WR == 1 ? sqrt(var) : var; }
     }
+    store_tile_striped(static_cast<O*>(out), blockIdx.x * TS, o, n, reinterpret_cast<O*>(stage_raw));
+}
+// varw / stddevw, windows of up to VAR_DIRECT_MAX_W: one tile per workgroup (var_short_tile)
+template <class T, bool SD, int RW>
+__global__ void __launch_bounds__(SB) var_short_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, double* __restrict__ out) {
+    __shared__ T L[TS + VAR_DIRECT_MAX_W];
+    var_short_tile<T, SD, RW>(x, n, w, [&](uint32_t p) { return p + 1 < w ? p + 1 : w; }, L, out);
+}
+// the moments scan of a whole column: WR as var_scan_kernel (workspace reset and sized by the caller)
+template <class T, int WR> int run_var_scan(aqg_ctx* ctx, const T* x, uint32_t n, void* out, bool timed = true) {
+    using A = typename mom_alg<T>::A;
+    const uint32_t ntiles = aqg_ceil_div(n, TS);
+    A *agg, *chunk_tot;
+    AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
+    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles / CH + 2, &chunk_tot));
+    hipLaunchKernelGGL((tile_reduce_kernel<T, mom_alg<T>>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg);
+    launch_agg_scan<mom_alg<T>>(ctx, agg, ntiles, chunk_tot);
+    if (timed) aqg_kernel_timer_begin(ctx);
+    hipLaunchKernelGGL((var_scan_kernel<T, WR>), dim3(ntiles), dim3(SB), (size_t)TS * (WR == 2 ? sizeof(dpair) : sizeof(double)), ctx->stream, x, n, agg, out);
+    if (timed) aqg_kernel_timer_end(ctx);
+    return aqg_check_launch(ctx, "var_scan_kernel");
+}
+size_t var_ws_bytes(uint32_t n) {
+    const size_t ntiles = aqg_ceil_div(n, TS);
+    return (ntiles + ntiles / CH + 2) * sizeof(mom_alg<double>::A) + 8192;
 }
 // out[i] = better(out[i], seed): the three-kernel fallback of a seeded running min / max
 template <class T, bool IS_MAX> __global__ void __launch_bounds__(SB) apply_seed_kernel(T* __restrict__ out, uint32_t n, T seed) {
@@ -802,14 +815,38 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
             aqg_kernel_timer_end(ctx);
             return aqg_check_launch(ctx, "ratiow");
         }
-        case AQG_SCAN_SUMW: case AQG_SCAN_AVGW: case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: {
+        case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: {
+            // the intended population variance of the last min(w, i + 1) rows (D9)
+            const uint32_t ww = w > n ? n : w;
+            const bool sd = op == AQG_SCAN_STDDEVW;
+            if (ww <= VAR_DIRECT_MAX_W) {
+                auto go = [&](auto kern) -> int {
+                    aqg_kernel_timer_begin(ctx);
+                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, ww, static_cast<double*>(out));
+                    aqg_kernel_timer_end(ctx);
+                    return aqg_check_launch(ctx, "var_short_kernel");
+                };
+                if (ww <= (uint32_t)VAR_REG_W) return sd ? go(&var_short_kernel<T, true, VAR_REG_W>) : go(&var_short_kernel<T, false, VAR_REG_W>);
+                return sd ? go(&var_short_kernel<T, true, 0>) : go(&var_short_kernel<T, false, 0>);
+            }
+            AQG_TRY(aqg_ws_reset(ctx));
+            AQG_TRY(aqg_ws_ensure(ctx, var_ws_bytes(n) + (size_t)n * sizeof(dpair) + 256));
+            dpair* P;
+            AQG_TRY(aqg_ws_get(ctx, n, &P));
+            aqg_kernel_timer_begin(ctx);                                        // the timer spans every pass: moments scan, difference
+            AQG_TRY((run_var_scan<T, 2>(ctx, x, n, P, /*timed=*/false)));
+            if (sd) hipLaunchKernelGGL((var_prefix_diff_kernel<true>), dim3(sgrid), dim3(SB), 0, ctx->stream, P, (const uint32_t*)nullptr, n, ww, static_cast<double*>(out));
+            else hipLaunchKernelGGL((var_prefix_diff_kernel<false>), dim3(sgrid), dim3(SB), 0, ctx->stream, P, (const uint32_t*)nullptr, n, ww, static_cast<double*>(out));
+            aqg_kernel_timer_end(ctx);
+            return aqg_check_launch(ctx, "wide window variance");
+        }
+        case AQG_SCAN_SUMW: case AQG_SCAN_AVGW: {
             using A = typename sum_alg<T>::A;
             uint32_t ww = w > n ? n : w;                                        // w clamped to len (:241,264)
-            const bool var = op == AQG_SCAN_VARW || op == AQG_SCAN_STDDEVW;
             const size_t ext = (size_t)TS + (ww - 1 + IT - 1) / IT * IT;            // tile + halo rounded up to whole blocks
-            size_t lds = var ? ext * sizeof(double) * 2 : ext * sizeof(A);
+            size_t lds = ext * sizeof(A);
             if constexpr (std::is_floating_point_v<T>) {
-                if (!var && ww <= 64) {
+                if (ww <= 64) {
                     aqg_kernel_timer_begin(ctx);
                     if (op == AQG_SCAN_SUMW) hipLaunchKernelGGL((window_direct_kernel<T, 0>), dim3(sgrid), dim3(SB), 0, ctx->stream, x, n, ww, static_cast<double*>(out));
                     else hipLaunchKernelGGL((window_direct_kernel<T, 1>), dim3(sgrid), dim3(SB), 0, ctx->stream, x, n, ww, static_cast<double*>(out));
@@ -825,14 +862,8 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
                     aqg_kernel_timer_end(ctx);
                     return aqg_check_launch(ctx, "window_sum_kernel");
                 };
-                switch (op) {
-                case AQG_SCAN_SUMW: return go(&window_sum_kernel<T, 0>);
-                case AQG_SCAN_AVGW: return go(&window_sum_kernel<T, 1>);
-                case AQG_SCAN_VARW: return go(&window_sum_kernel<T, 2>);
-                default: return go(&window_sum_kernel<T, 3>);
-                }
+                return op == AQG_SCAN_SUMW ? go(&window_sum_kernel<T, 0>) : go(&window_sum_kernel<T, 1>);
             }
-            if (var) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_scan: varw/stddevw window too large for the LDS halo");
             // wide window: global inclusive prefix, then the difference
             AQG_TRY(aqg_ws_reset(ctx));
             AQG_TRY(aqg_ws_ensure(ctx, (size_t)ntiles * sizeof(A) + (size_t)n * sizeof(A) + 8192));
@@ -929,17 +960,8 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
         }
         case AQG_SCAN_VARS: case AQG_SCAN_STDDEVS: {
             AQG_TRY(aqg_ws_reset(ctx));
-            AQG_TRY(aqg_ws_ensure(ctx, (size_t)ntiles * 16 + 8192));
-            double *a1, *a2;
-            AQG_TRY(aqg_ws_get(ctx, ntiles, &a1));
-            AQG_TRY(aqg_ws_get(ctx, ntiles, &a2));
-            hipLaunchKernelGGL((tile_reduce_kernel<T, dsum_alg<T>>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, a1);
-            hipLaunchKernelGGL((tile_reduce_kernel<T, sq_alg<T>>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, a2);
-            hipLaunchKernelGGL((agg_scan_kernel<dsum_alg<T>>), dim3(1), dim3(SB), 0, ctx->stream, a1, ntiles);
-            hipLaunchKernelGGL((agg_scan_kernel<dsum_alg<T>>), dim3(1), dim3(SB), 0, ctx->stream, a2, ntiles);
-            if (op == AQG_SCAN_VARS) hipLaunchKernelGGL((vars_kernel<T, false>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, a1, a2, static_cast<double*>(out));
-            else hipLaunchKernelGGL((vars_kernel<T, true>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, a1, a2, static_cast<double*>(out));
-            return aqg_check_launch(ctx, "vars");
+            AQG_TRY(aqg_ws_ensure(ctx, var_ws_bytes(n)));
+            return op == AQG_SCAN_VARS ? run_var_scan<T, 0>(ctx, x, n, out) : run_var_scan<T, 1>(ctx, x, n, out);
         }
         }
         return AQG_ERR_ARG;

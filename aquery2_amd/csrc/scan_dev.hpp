@@ -143,6 +143,97 @@ template <class T> struct sq_alg {   // tile aggregate of x*x in double
     __device__ static double lift(T v) { return (double)v * (double)v; }
     __device__ static double op(double a, double b) { return a + b; }
 };
+struct dpair { double s, q; };
+
+// ---- variance scans (vars / stddevs / varw / stddevw) --------------------------------------------------------------------------
+// Variance does not change when a constant is added to the data, but E[x^2] - E[x]^2 from raw sums loses everything to
+// cancellation once mean^2 dwarfs the spread (int32 near 2^31: relative errors ~1e-1).  Every variance path here works on
+// differences x - K from an anchor K that is itself an element of the data, so the terms are bounded by the range of the values.
+// x - K, computed in the column's own arithmetic: exact for integers (two's complement, |x - K| < 2^63) and representable as a
+// double while |x - K| < 2^53; for floating columns one rounding at most (none when x and K are within a factor of two)
+template <class T> __device__ inline double anchored(T x, T k) {
+    if constexpr (std::is_floating_point_v<T>) return (double)x - (double)k;
+    else return (double)(int64_t)((uint64_t)x - (uint64_t)k);
+}
+// moments about an anchor: k = the first element of the range, s = sum (x - k), q = sum (x - k)^2, n = elements.  The combine
+// moves b onto a's anchor: sum (x - ka) = s_b + n_b d, sum (x - ka)^2 = q_b + 2 d s_b + n_b d^2 with d = kb - ka (exact for
+// integers), whose terms are bounded by n_b (range)^2 as well.  Identity: n = 0.
+template <class T> struct mom_alg {
+    struct A { T k; uint32_t n; double s, q; };
+    __device__ static A identity() { A r; r.k = (T)0; r.n = 0; r.s = 0; r.q = 0; return r; }
+    __device__ static A lift(T v) { A r; r.k = v; r.n = 1; r.s = 0; r.q = 0; return r; }
+    __device__ static A op(A a, A b) {
+        if (!b.n) return a;
+        if (!a.n) return b;
+        const double d = anchored(b.k, a.k), nb = (double)b.n;
+        A r;
+        r.k = a.k;
+        r.n = a.n + b.n;
+        r.s = a.s + (b.s + nb * d);
+        r.q = a.q + (b.q + (2.0 * d * b.s + nb * d * d));
+        return r;
+    }
+};
+// population variance of n elements from their anchored sums (0 when every difference is 0)
+__device__ inline double var_from(double s, double q, double n) {
+    const double v = (q - s * s / n) / n;
+    return v > 0 ? v : 0.0;
+}
+constexpr uint32_t VAR_DIRECT_MAX_W = 64;         // longer windows take the anchored prefix difference below
+constexpr int VAR_REG_W = 8;                      // windows up to this long keep their differences in registers
+// varw / stddevw over one tile of TS positions, windows of up to VAR_DIRECT_MAX_W (len_of(p) = the window's length at p, 1..w):
+// the tile and its w - 1 row halo are staged in LDS with coalesced loads, lane t takes positions t, t + SB, ... (conflict-free LDS
+// reads, coalesced stores).  Two passes over the window: the mean of the differences from an anchor inside the window, then the
+// squared deviations from it -- no cancellation against anything wider than the window.  RW > 0: the window's differences
+// (w <= RW) are kept in registers, RW == 0: both passes read LDS.
+template <class T, bool SD, int RW, class LEN>
+__device__ inline void var_short_tile(const T* __restrict__ x, uint32_t n, uint32_t w, LEN len_of, T* L /* TS + VAR_DIRECT_MAX_W */, double* __restrict__ out) {
+    const uint32_t H = w - 1, tile_start = blockIdx.x * TS;
+    for (uint32_t q = threadIdx.x; q < H + TS; q += SB) {
+        const int64_t g = (int64_t)tile_start - (int64_t)H + q;
+        L[q] = (g >= 0 && g < (int64_t)n) ? x[g] : (T)0;
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < TS; j += SB) {
+        const uint32_t p = tile_start + j;
+        if (p >= n) break;
+        const uint32_t len = len_of(p), idx = H + j;            // L[idx] holds row p; len <= w, so idx + 1 - len >= 0
+        double var;
+        if constexpr (RW > 0) {
+            const T k = L[idx];                                   // anchor: the position's own element
+            double d[RW], s = 0;
+#pragma unroll
+            for (int e = 0; e < RW; ++e) { d[e] = (uint32_t)e < len ? anchored(L[idx - e], k) : 0.0; s += d[e]; }
+            const double m = s / (double)len;
+            double q = 0;
+#pragma unroll
+            for (int e = 0; e < RW; ++e) if ((uint32_t)e < len) { const double t = d[e] - m; q += t * t; }
+            var = q / (double)len;
+        } else {
+            const uint32_t lo = idx + 1 - len;
+            const T k = L[lo];                                    // anchor: the window's first element
+            double s = 0;
+            for (uint32_t e = lo + 1; e <= idx; ++e) s += anchored(L[e], k);
+            const double m = s / (double)len;
+            double q = 0;
+            for (uint32_t e = lo; e <= idx; ++e) { const double t = anchored(L[e], k) - m; q += t * t; }
+            var = q / (double)len;
+        }
+        out[p] = SD ? sqrt(var) : var;
+    }
+}
+// windows of any length: P[i] = anchored sums of x over [first of the group (of the column when D is null) .. i], one anchor per
+// group; the window is the difference of two of them.  D[i] = predecessors of i inside its group.
+template <bool SD>
+__global__ void __launch_bounds__(SB) var_prefix_diff_kernel(const dpair* __restrict__ P, const uint32_t* __restrict__ D, uint32_t n, uint32_t w, double* __restrict__ out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t d = D ? D[i] : i, len = d + 1 < w ? d + 1 : w;
+        dpair a = P[i];
+        if (len <= d) { const dpair b = P[i - len]; a.s -= b.s; a.q -= b.q; }
+        const double v = var_from(a.s, a.q, (double)len);
+        out[i] = SD ? sqrt(v) : v;
+    }
+}
 
 
 // K2: exclusive scan of the tile aggregates by one workgroup

@@ -8,8 +8,9 @@
 // scan.hip segmented:
 //   prefix scans (sums / avgs / mins / maxs / vars / stddevs): reduce-then-scan over 2048-position tiles with the carry
 //       {value, last group start, groups so far} -- a group start resets the value;
-//   windows (sumw / avgw / varw / stddevw, minw / maxw): tile + halo in LDS as in scan.hip, every window clamped at its group's start
-//       (no carry between tiles: a window never reaches back further than the halo);
+//   windows (sumw / avgw, minw / maxw): tile + halo in LDS as in scan.hip, every window clamped at its group's start
+//       (no carry between tiles: a window never reaches back further than the halo); varw / stddevw: two passes over windows of up
+//       to 64 positions, longer ones from a segmented prefix of moments about the group's first element (any w);
 //   shifts (deltas / prev / aggnext / ratiow): neighbour loads guarded by the start bits.
 // Integer results are exact; floating sums follow the tile order (tolerance as for the whole-column scans).
 // HBM-bound: sizeof(T) + sizeof(out) bytes per row for the scan proper, 12 (one radix pass, <= 256 groups) to 20 x passes for flatten.
@@ -29,13 +30,6 @@ template <class ALG> struct seg_alg {
     using A = SegCarry<typename ALG::A>;
     __device__ static A identity() { A r; r.v = ALG::identity(); r.s = 0; r.c = 0; return r; }
     __device__ static A op(A a, A b) { A r; r.s = b.s ? b.s : a.s; r.c = a.c + b.c; r.v = b.s ? b.v : ALG::op(a.v, b.v); return r; }
-};
-struct dpair { double s, q; };
-template <class T> struct var2_alg {          // running sum and sum of squares in double (vars / stddevs, as vars_kernel of scan.hip)
-    using A = dpair;
-    __device__ static dpair identity() { return {0.0, 0.0}; }
-    __device__ static dpair lift(T v) { const double d = (double)v; return {d, d * d}; }
-    __device__ static dpair op(dpair a, dpair b) { return {a.s + b.s, a.q + b.q}; }
 };
 struct ipair { int64_t s, q; };
 // sum and sum of squares of a group for var / stddev (aggregations.h:332-348): exact for integer columns of up to four bytes -- x * x in the
@@ -114,12 +108,12 @@ __global__ void __launch_bounds__(SB) seg_tile_reduce_kernel(const T* __restrict
     if (threadIdx.x == 0) tile_carry[blockIdx.x] = total;
 }
 
-enum : int { SW_SUMS = 0, SW_AVGS, SW_MINS, SW_MAXS, SW_MAXP, SW_VARS, SW_STDDEVS, SW_RAW, SW_DIST, SW_GID, SW_RED_SUM, SW_RED_AVG, SW_RED_MIN, SW_RED_MAX, SW_RED_VAR, SW_RED_STDDEV };
+enum : int { SW_SUMS = 0, SW_AVGS, SW_MINS, SW_MAXS, SW_MAXP, SW_VARS, SW_STDDEVS, SW_RAW, SW_MOM, SW_DIST, SW_GID, SW_RED_SUM, SW_RED_AVG, SW_RED_MIN, SW_RED_MAX, SW_RED_VAR, SW_RED_STDDEV };
 template <class T, int WR> struct seg_out {
     using type = std::conditional_t<WR == SW_SUMS || WR == SW_RED_SUM, std::conditional_t<std::is_floating_point_v<T>, double, aqg_i128>,
                  std::conditional_t<WR == SW_AVGS || WR == SW_VARS || WR == SW_STDDEVS || WR == SW_RED_AVG || WR == SW_RED_VAR || WR == SW_RED_STDDEV, double,
-                 std::conditional_t<WR == SW_RAW, typename sum_alg<T>::A,
-                 std::conditional_t<WR == SW_DIST || WR == SW_GID, uint32_t, T>>>>;
+                 std::conditional_t<WR == SW_RAW, typename sum_alg<T>::A, std::conditional_t<WR == SW_MOM, dpair,
+                 std::conditional_t<WR == SW_DIST || WR == SW_GID, uint32_t, T>>>>>;
 };
 template <class T, class ALG, int WR>
 __global__ void __launch_bounds__(SB) seg_tile_scan_kernel(const T* __restrict__ x, uint32_t n, const uint8_t* __restrict__ heads8,
@@ -165,9 +159,8 @@ __global__ void __launch_bounds__(SB) seg_tile_scan_kernel(const T* __restrict__
         } else if constexpr (WR == SW_AVGS || WR == SW_RED_AVG) o[j] = sum_alg<T>::to_double(run) / rows;       // (s += arr[i]) / (double)(i + 1)
         else if constexpr (WR == SW_MINS || WR == SW_MAXP || WR == SW_RED_MIN) o[j] = run;
         else if constexpr (WR == SW_MAXS || WR == SW_RED_MAX) { T seed = dlimits<T>::min(); o[j] = seed > run ? seed : run; }    // max / maxs seed with numeric_limits<T>::min() (D8)
-        else if constexpr (WR == SW_VARS || WR == SW_STDDEVS) {
-            double var = (run.q - run.s * run.s / rows) / rows;
-            if (var < 0) var = 0;
+        else if constexpr (WR == SW_VARS || WR == SW_STDDEVS) {                  // anchored moments of the group so far (mom_alg)
+            const double var = var_from(run.s, run.q, (double)run.n);
             o[j] = WR == SW_STDDEVS ? sqrt(var) : var;
         } else if constexpr (WR == SW_RED_VAR || WR == SW_RED_STDDEV) {          // (ssq - s * s / (FPType)(len + 1)) / (FPType)(len + 1): D9 kept
             const double np1 = (double)(uint32_t)(p - s + 3);
@@ -179,6 +172,7 @@ __global__ void __launch_bounds__(SB) seg_tile_scan_kernel(const T* __restrict__
             }
             o[j] = WR == SW_RED_STDDEV ? sqrt(d) : d;
         } else if constexpr (WR == SW_RAW) o[j] = run;
+        else if constexpr (WR == SW_MOM) o[j] = dpair{run.s, run.q};
         else if constexpr (WR == SW_DIST) o[j] = p - (s - 1);
         else o[j] = c - 1;
         if constexpr (RED) {
@@ -263,23 +257,21 @@ __global__ void __launch_bounds__(SB) seg_shift4_kernel(const T* __restrict__ x,
     }
 }
 
-// ---- sliding sums (sumw / avgw / varw / stddevw): window_sum_kernel of scan.hip with every window clamped at its group's start ----------
+// ---- sliding sums (sumw / avgw): window_sum_kernel of scan.hip with every window clamped at its group's start ----------
 template <class T, int MODE>
 __global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, const uint8_t* __restrict__ heads8, void* __restrict__ out) {
-    using ALG = std::conditional_t<(MODE >= 2), dsum_alg<T>, sum_alg<T>>;
+    using ALG = sum_alg<T>;
     using A = typename ALG::A;
     using MX = max_alg<uint32_t>;
     extern __shared__ __align__(16) unsigned char smem_raw[];
     __shared__ A lds_w[8];
-    __shared__ A lds_w2[8];
     __shared__ uint32_t lds_m[8];
     const uint32_t tile_start = blockIdx.x * TS, tile_end = tile_start + TS < n ? tile_start + TS : n;
     const uint32_t H = (w - 1 + IT - 1) / IT * IT;                // LDS position p <-> row tile_start - H + p
     const uint32_t L = H + TS, nblk = L / IT;
     A* S = reinterpret_cast<A*>(smem_raw);
-    A* Q = S + (MODE >= 2 ? L : 0);
-    uint32_t* LH = reinterpret_cast<uint32_t*>(Q + L);            // per block of IT positions: {position + 1 of the last group start BEFORE the block (0: none in this tile), the block's start bits : 8}
-    A carry = ALG::identity(), carry2 = ALG::identity();
+    uint32_t* LH = reinterpret_cast<uint32_t*>(S + L);            // per block of IT positions: {position + 1 of the last group start BEFORE the block (0: none in this tile), the block's start bits : 8}
+    A carry = ALG::identity();
     uint32_t carry_m = 0;
     for (uint32_t blk0 = 0; blk0 < nblk; blk0 += SB) {
         const uint32_t blk = blk0 + threadIdx.x;
@@ -295,26 +287,20 @@ __global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict_
         }
         const uint32_t hb = (blk < nblk && g0 >= 0 && g0 < (int64_t)n) ? heads8[g0 >> 3] : 0u;
         const uint32_t lh = hb ? blk * IT + (31 - __clz((int)hb)) + 1 : 0u;
-        A loc[IT], loc2[IT];
-        A a = ALG::identity(), q = ALG::identity();
+        A loc[IT];
+        A a = ALG::identity();
 #pragma unroll
-        for (int j = 0; j < IT; ++j) {
-            a = ALG::op(a, ALG::lift(v[j])); loc[j] = a;
-            if constexpr (MODE >= 2) { q = q + (double)v[j] * (double)v[j]; loc2[j] = q; }
-        }
-        A tot, tot2;
+        for (int j = 0; j < IT; ++j) { a = ALG::op(a, ALG::lift(v[j])); loc[j] = a; }
+        A tot;
         A excl = ALG::op(carry, block_scan_excl<ALG>(a, lds_w, tot));
-        A excl2 = ALG::identity();
-        if constexpr (MODE >= 2) excl2 = ALG::op(carry2, block_scan_excl<ALG>(q, lds_w2, tot2));
         uint32_t totm;
         const uint32_t before = MX::op(carry_m, block_scan_excl<MX>(lh, lds_m, totm));
         if (blk < nblk) {
 #pragma unroll
-            for (int j = 0; j < IT; ++j) { S[blk * IT + j] = ALG::op(excl, loc[j]); if constexpr (MODE >= 2) Q[blk * IT + j] = ALG::op(excl2, loc2[j]); }
+            for (int j = 0; j < IT; ++j) S[blk * IT + j] = ALG::op(excl, loc[j]);
             LH[blk] = (before << 8) | hb;
         }
         carry = ALG::op(carry, tot);
-        if constexpr (MODE >= 2) carry2 = ALG::op(carry2, tot2);
         carry_m = MX::op(carry_m, totm);
     }
     __syncthreads();
@@ -329,14 +315,8 @@ __global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict_
         if constexpr (MODE == 0) {
             if constexpr (std::is_floating_point_v<T>) static_cast<double*>(out)[i] = s;
             else static_cast<aqg_i128*>(out)[i] = ALG::to_i128(s);
-        } else if constexpr (MODE == 1) {
-            static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
         } else {
-            A sq = lower ? ALG::sub(Q[idx], Q[lower - 1]) : Q[idx];
-            double mean = ALG::to_double(s) / (double)len;
-            double var = ALG::to_double(sq) / (double)len - mean * mean;
-            if (var < 0) var = 0;
-            static_cast<double*>(out)[i] = MODE == 3 ? sqrt(var) : var;
+            static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
         }
     }
 }
@@ -351,6 +331,12 @@ __global__ void __launch_bounds__(SB) seg_window_direct_kernel(const T* __restri
         for (uint32_t j = i + 1 - len; j <= i; ++j) s += (double)x[j];
         out[i] = MODE == 0 ? s : s / (double)len;
     }
+}
+// varw / stddevw, windows of up to VAR_DIRECT_MAX_W: var_short_tile with every window clamped at its group's start
+template <class T, bool SD, int RW>
+__global__ void __launch_bounds__(SB) seg_var_short_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, const uint32_t* __restrict__ heads, double* __restrict__ out) {
+    __shared__ T L[TS + VAR_DIRECT_MAX_W];
+    var_short_tile<T, SD, RW>(x, n, w, [&](uint32_t p) { return dist_to_head(heads, p, w - 1) + 1; }, L, out);
 }
 // windows wider than the LDS halo: a segmented inclusive prefix S (SW_RAW) and the distance D of every position to its group's start
 template <class T, int MODE>
@@ -555,14 +541,14 @@ int ensure_short(aqg_ctx* ctx, aqg_groupby* g, uint32_t w) {
 
 size_t carry_ws_bytes(uint32_t n) {
     const size_t ntiles = aqg_ceil_div(n, TS);
-    return ntiles * 32 + (ntiles / CH + 2) * 32 + 4096;
+    return ntiles * 48 + (ntiles / CH + 2) * 48 + 4096;
 }
 // one segmented prefix pass (workspace already sized): carries -> their scan -> results
 template <class T, class ALG, int WR>
 int seg_prefix(aqg_ctx* ctx, aqg_groupby* g, const T* x, uint32_t n, void* out) {
     using C = SegCarry<typename ALG::A>;
     using O = typename seg_out<T, WR>::type;
-    static_assert(sizeof(C) <= 32, "carry_ws_bytes");
+    static_assert(sizeof(C) <= 48, "carry_ws_bytes");
     const uint32_t ntiles = aqg_ceil_div(n, TS);
     const uint8_t* heads8 = reinterpret_cast<const uint8_t*>(g->flat_heads);
     C *carry, *chunk_tot;
@@ -583,6 +569,7 @@ size_t scan_ws_bytes(int op, int t, uint32_t n, uint32_t w) {
     switch (op) {
     case AQG_SCAN_SUMW: case AQG_SCAN_AVGW: need += (size_t)n * (4 + 16) + 8192; break;          // (only the wide-window path uses them)
     case AQG_SCAN_MINW: case AQG_SCAN_MAXW: need += (size_t)n * (4 + 2 * esz) + 8192; break;
+    case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: need += (size_t)n * (4 + sizeof(dpair)) + 8192; break;   // (windows longer than VAR_DIRECT_MAX_W)
     default: break;
     }
     (void)w;
@@ -619,18 +606,39 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
         case AQG_SCAN_AVGS: return seg_prefix<T, sum_alg<T>, SW_AVGS>(ctx, g, x, n, out);
         case AQG_SCAN_MINS: return seg_prefix<T, min_alg<T>, SW_MINS>(ctx, g, x, n, out);
         case AQG_SCAN_MAXS: return seg_prefix<T, max_alg<T>, SW_MAXS>(ctx, g, x, n, out);
-        case AQG_SCAN_VARS: return seg_prefix<T, var2_alg<T>, SW_VARS>(ctx, g, x, n, out);
-        case AQG_SCAN_STDDEVS: return seg_prefix<T, var2_alg<T>, SW_STDDEVS>(ctx, g, x, n, out);
+        case AQG_SCAN_VARS: return seg_prefix<T, mom_alg<T>, SW_VARS>(ctx, g, x, n, out);
+        case AQG_SCAN_STDDEVS: return seg_prefix<T, mom_alg<T>, SW_STDDEVS>(ctx, g, x, n, out);
+        case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: {
+            const bool sd = op == AQG_SCAN_STDDEVW;
+            const uint32_t ww = w > n ? n : w;
+            if (ww <= VAR_DIRECT_MAX_W) {
+                auto go = [&](auto kern) -> int {
+                    aqg_kernel_timer_begin(ctx);
+                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, ww, heads, static_cast<double*>(out));
+                    aqg_kernel_timer_end(ctx);
+                    return aqg_check_launch(ctx, "seg_var_short_kernel");
+                };
+                if (ww <= (uint32_t)VAR_REG_W) return sd ? go(&seg_var_short_kernel<T, true, VAR_REG_W>) : go(&seg_var_short_kernel<T, false, VAR_REG_W>);
+                return sd ? go(&seg_var_short_kernel<T, true, 0>) : go(&seg_var_short_kernel<T, false, 0>);
+            }
+            dpair* P; uint32_t* D;
+            AQG_TRY(aqg_ws_get(ctx, n, &P));
+            AQG_TRY(aqg_ws_get(ctx, n, &D));
+            AQG_TRY((seg_prefix<T, mom_alg<T>, SW_MOM>(ctx, g, x, n, P)));
+            AQG_TRY(dist_column(ctx, g, n, D));
+            if (sd) hipLaunchKernelGGL((var_prefix_diff_kernel<true>), dim3(egrid), dim3(SB), 0, ctx->stream, P, D, n, ww, static_cast<double*>(out));
+            else hipLaunchKernelGGL((var_prefix_diff_kernel<false>), dim3(egrid), dim3(SB), 0, ctx->stream, P, D, n, ww, static_cast<double*>(out));
+            return aqg_check_launch(ctx, "wide window variance (grouped)");
+        }
         case AQG_SCAN_DELTAS: return al16 ? shift4(&seg_shift4_kernel<T, AQG_SCAN_DELTAS>, "deltas (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_DELTAS>, "deltas (grouped)");
         case AQG_SCAN_PREV: return al16 ? shift4(&seg_shift4_kernel<T, AQG_SCAN_PREV>, "prev (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_PREV>, "prev (grouped)");
         case AQG_SCAN_NEXT: return al16 ? shift4(&seg_shift4_kernel<T, AQG_SCAN_NEXT>, "aggnext (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_NEXT>, "aggnext (grouped)");
         case AQG_SCAN_RATIOW: return (al16 && w == 1) ? shift4(&seg_shift4_kernel<T, AQG_SCAN_RATIOW>, "ratios (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_RATIOW>, "ratiow (grouped)");
-        case AQG_SCAN_SUMW: case AQG_SCAN_AVGW: case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: {
+        case AQG_SCAN_SUMW: case AQG_SCAN_AVGW: {
             using A = typename sum_alg<T>::A;
             const uint32_t ww = w > n ? n : w;                                          // (a window is clamped by its group anyway)
-            const bool var = op == AQG_SCAN_VARW || op == AQG_SCAN_STDDEVW;
             if constexpr (std::is_floating_point_v<T>) {
-                if (!var && ww <= 64) {
+                if (ww <= 64) {
                     aqg_kernel_timer_begin(ctx);
                     if (op == AQG_SCAN_SUMW) hipLaunchKernelGGL((seg_window_direct_kernel<T, 0>), dim3(egrid), dim3(SB), 0, ctx->stream, x, n, ww, heads, static_cast<double*>(out));
                     else hipLaunchKernelGGL((seg_window_direct_kernel<T, 1>), dim3(egrid), dim3(SB), 0, ctx->stream, x, n, ww, heads, static_cast<double*>(out));
@@ -639,7 +647,7 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
                 }
             }
             const size_t ext = (size_t)TS + (ww - 1 + IT - 1) / IT * IT;
-            const size_t lds = (var ? ext * sizeof(double) * 2 : ext * sizeof(A)) + ext / IT * 4 + 16;
+            const size_t lds = ext * sizeof(A) + ext / IT * 4 + 16;
             if (lds <= HALO_MAX_BYTES) {
                 auto go = [&](auto kern) -> int {
                     AQG_TRY(aqg_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
@@ -648,14 +656,8 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
                     aqg_kernel_timer_end(ctx);
                     return aqg_check_launch(ctx, "seg_window_sum_kernel");
                 };
-                switch (op) {
-                case AQG_SCAN_SUMW: return go(&seg_window_sum_kernel<T, 0>);
-                case AQG_SCAN_AVGW: return go(&seg_window_sum_kernel<T, 1>);
-                case AQG_SCAN_VARW: return go(&seg_window_sum_kernel<T, 2>);
-                default: return go(&seg_window_sum_kernel<T, 3>);
-                }
+                return op == AQG_SCAN_SUMW ? go(&seg_window_sum_kernel<T, 0>) : go(&seg_window_sum_kernel<T, 1>);
             }
-            if (var) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_grouped_scan: varw/stddevw window too large for the LDS halo");
             A* S; uint32_t* D;
             AQG_TRY(aqg_ws_get(ctx, n, &S));
             AQG_TRY(aqg_ws_get(ctx, n, &D));

@@ -152,7 +152,8 @@ int aqg_corr(aqg_ctx* ctx, int tx, const void* x, int ty, const void* y, uint32_
 
 /* ---- prefix scans, sliding windows, shifts ---------------------------------
  * sums/avgs/mins/maxs  server/aggregations.h:89-125,203-236
- * sumw/avgw/minw/maxw/ratiow :127-191,238-281 ; varw/stddevw :283-330 (D9, unpinned)
+ * sumw/avgw/minw/maxw/ratiow :127-191,238-281 ; varw/stddevw :283-330 (D9: out-of-bounds read in the reference;
+ *   here the population variance of the last min(w, i+1) rows, held to tests/test_gpu_variance.py)
  * deltas/prev/aggnext :439-485 ; ratios = ratiow(1) :193-201 ; vars/stddevs :350-381
  * window = elements [i-w+1, i]; growing prefix for i < w.                      */
 typedef enum aqg_scanop {

@@ -5,6 +5,9 @@
 //   dll_q7      benchmark/quries/Aquery/q7.a   SELECT stocksymbol, avgs(5, price) FROM trade ASSUMING ASC time GROUP BY stocksymbol
 //   dll_memopt  mem_opt.cpp:28-65              the older AQHashTable shape: avgw(10, sales[vecs[i]], col[i]) into buf + offsets
 //   dll_q4      tests/q4.a:23                  SELECT ID, max(ratios(endofdayprice)), min(ratios(endofdayprice)) FROM ticks GROUP BY ID
+//   dll_q10     benchmark/quries/Aquery/q10.a  SELECT stocksymbol, MAX(stddevs(3, price)) FROM trade ASSUMING ASC time GROUP BY stocksymbol
+//                                              (common/types.py:289 emits the two-argument stddevs as stddevw)
+//   dll_q10w    the q7 shape with varw(5000, price[val], col[i]): a window far wider than any LDS halo, through Runtime::vcol_scan
 //   dll_q9      benchmark/h2o/groupby.sql:20   SELECT id2, id4, pow(corr(v1, v2), 2) AS r2 FROM source GROUP BY id2, id4
 //   dll_q8      benchmark/h2o/groupby.sql:17   SELECT id6, subvec(v3,0,2) AS v3 FROM source GROUP BY id6   (engine/expr.py:237: `v3[val].subvec(0, 2)`)
 //   dll_expr    tests/stock.a:24 per symbol    SELECT sym, max(price - mins(price)), sum(price + price), mins(2, price) ... GROUP BY sym
@@ -246,6 +249,78 @@ GC::scratch_space->release();
 }
 GC::scratch_space = nullptr;
 aqtest::dump_table("q8.out", *out_5e);
+puts("done.");
+return 0;
+}
+
+__AQEXPORT__(int) dll_q10(Context* cxt) {
+	using namespace std;
+	using namespace types;
+	auto server = static_cast<DataSource*>(cxt->curr_server);
+auto len_1a = server->cnt;
+auto stocksymbol_2b = ColRef<int>(len_1a, server->getCol(0, types::Type_t::AINT32));
+auto price_3c = ColRef<int>(len_1a, server->getCol(1, types::Type_t::AINT32));
+const char* names_4d[] = {"stocksymbol", "MAXstddevs3yprice"};
+auto out_5e = new TableInfo<int,value_type<decays<decltype(max(stddevw(3, price_3c)))>>>("out_5e", names_4d);
+decltype(auto) col_6f = out_5e->get_col<0>();
+decltype(auto) col_7g = out_5e->get_col<1>();
+uint32_t len_8h = stocksymbol_2b.size;
+typedef record<decays<decltype(stocksymbol_2b)>::value_t> record_type9i;
+auto g10j = HashTableFactory<record_type9i, transTypes<record_type9i, hasher>>::get<decays<decltype(stocksymbol_2b)>>(stocksymbol_2b);
+auto sz_g10j = g10j.size;
+auto vecs_11k = g10j.values;
+col_6f.resize(sz_g10j);
+col_7g.resize(sz_g10j);
+GC::scratch_space = GC::gc_handle ? &(GC::gc_handle->scratch) : nullptr;
+for (uint32_t i12 = 0; i12 < sz_g10j; ++i12) {
+auto &key_13l = (*g10j.keys)[i12];
+auto &val_14m = vecs_11k[i12];
+col_6f[i12] = (get<0>(key_13l));
+
+col_7g[i12] = (max(stddevw(3, price_3c[val_14m])));
+
+GC::scratch_space->release();
+}
+GC::scratch_space = nullptr;
+aqtest::dump_table("q10.out", *out_5e);
+puts("done.");
+return 0;
+}
+
+__AQEXPORT__(int) dll_q10w(Context* cxt) {
+	using namespace std;
+	using namespace types;
+	auto server = static_cast<DataSource*>(cxt->curr_server);
+auto len_1a = server->cnt;
+auto stocksymbol_2b = ColRef<int>(len_1a, server->getCol(0, types::Type_t::AINT32));
+auto price_3c = ColRef<int>(len_1a, server->getCol(1, types::Type_t::AINT32));
+const char* names_4d[] = {"stocksymbol", "varw5000yprice"};
+auto out_5e = new TableInfo<int,vector_type<value_type<decays<decltype(varw(5000, price_3c))>>>>("out_5e", names_4d);
+decltype(auto) col_6f = out_5e->get_col<0>();
+decltype(auto) col_7g = out_5e->get_col<1>();
+uint32_t len_8h = stocksymbol_2b.size;
+typedef record<decays<decltype(stocksymbol_2b)>::value_t> record_type9i;
+auto g10j = HashTableFactory<record_type9i, transTypes<record_type9i, hasher>>::get<decays<decltype(stocksymbol_2b)>>(stocksymbol_2b);
+auto sz_g10j = g10j.size;
+auto vecs_11k = g10j.values;
+col_6f.resize(sz_g10j);
+col_7g.resize(sz_g10j);
+auto buf_col_7g = static_cast<double *>(calloc(len_8h, sizeof(double)));
+for (uint32_t i12 = 0; i12 < sz_g10j; ++i12) {
+col_7g[i12].init_from(vecs_11k[i12].size, buf_col_7g + g10j.offsets[i12]);
+}
+GC::scratch_space = GC::gc_handle ? &(GC::gc_handle->scratch) : nullptr;
+for (uint32_t i13 = 0; i13 < sz_g10j; ++i13) {
+auto &key_14l = (*g10j.keys)[i13];
+auto &val_15m = vecs_11k[i13];
+col_6f[i13] = (get<0>(key_14l));
+
+varw(5000, price_3c[val_15m], col_7g[i13]);
+
+GC::scratch_space->release();
+}
+GC::scratch_space = nullptr;
+aqtest::dump_table("q10w.out", *out_5e);
 puts("done.");
 return 0;
 }

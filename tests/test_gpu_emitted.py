@@ -353,6 +353,41 @@ def test_per_group_windows_into_the_flat_buffer(tmp_path, oracle, dataset, n, S)
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dataset,n,S", [("trade_small", 50_000, 300), ("trade", 10_000_000, 100_000)])
+def test_q10_per_group_stddevw_and_a_wide_varw(tmp_path, oracle, dataset, n, S):
+    """benchmark/quries/Aquery/q10.a `MAX(stddevs(3, price)) ... GROUP BY stocksymbol`, emitted as max(stddevw(3, price[val])), and
+    varw(5000, price[val], col[i]) into the flat buffer -- a window wider than any LDS halo, which Runtime::vcol_scan would turn into a
+    process abort on an error status -- for 1e5 symbols over 1e7 rows, without a launch per group"""
+    import time
+    import numpy as np
+    import checker as ck
+    import exact_moments as em
+    build()
+    sym, price = _trade(n, S)
+    ogb = oracle.groupby([sym])
+    t0 = time.time()
+    run("group_scans.so", dataset, "dll_q10", "dll_q10w", cwd=str(tmp_path))
+    dt = time.time() - t0
+    for name in ("q10", "q10w"):
+        assert np.array_equal(np.fromfile(tmp_path / f"{name}.out.0", np.int32), sym[ogb["first_rows"]]), name
+    flat_gb = dict(ngroups=ogb["ngroups"], offsets=ogb["offsets"], counts=ogb["counts"], row_ids=np.arange(n, dtype=np.uint32))
+    sd3 = _compose(oracle, ogb, price, lambda v: oracle.scan(ck.SCAN_NAMES["stddevw"], v, 3), np.float64)
+    want = oracle.grouped_reduce(ck.RED_MAX, sd3, flat_gb)
+    got = np.fromfile(tmp_path / "q10.out.1", np.float64)
+    assert got.size == ogb["ngroups"] and np.all(np.abs(got - want) <= 1e-12 * want + 1e-12)
+    xf = price[ogb["row_ids"]]
+    ex = em.Exact(xf, ogb["offsets"])
+    got = np.fromfile(tmp_path / "q10w.out.1", np.float64)
+    assert got.size == n
+    ex.check(got, ex.var(5000), 5000, what=f"q10w {dataset}")
+    if n * 5000 <= 10**9:
+        want = _compose(oracle, ogb, price, lambda v: oracle.scan(ck.SCAN_NAMES["varw"], v, 5000), np.float64)
+        b, _ = em.bound(xf, ex.var(5000), 5000, ogb["offsets"])
+        assert np.all(np.abs(got - want) <= b + 1e-12 * want)
+    assert dt < 120, f"{dt:.1f} s: the per-group scans must not cost a launch per group"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dataset,n,S", [("trade_small", 50_000, 300), ("trade", 10_000_000, 100_000)])
 def test_reductions_of_per_group_scans_and_expressions(tmp_path, oracle, dataset, n, S):
     """tests/q4.a:23 `max(ratios(x)), min(ratios(x)) GROUP BY ID` and per-symbol forms of tests/stock.a's expressions
     (`max(price - mins(price))`, `sum(price + price)`, `sum(price - 100)`, mins(2, price) into the flat buffer)"""

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import checker as ck
+import exact_moments as em
 import golden_util as gu
 from test_gpu_basic import rand
 
@@ -68,6 +69,7 @@ def test_flatten_is_the_gather_through_the_row_lists(gpu, oracle, esz_dtype, n, 
 
 SCANS = ["sums", "avgs", "mins", "maxs", "deltas", "prev", "aggnext"]
 WINDOWS = ["sumw", "avgw", "minw", "maxw", "ratiow"]
+FUZZ_W = [1, 2, 3, 5, 10, 64, 100, 1000, 2500, 30_000]
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("AQG_FUZZ_SEEDS", "40"))))
@@ -85,6 +87,20 @@ def test_grouped_scan_random_shapes(gpu, oracle, seed):
     xf = x[ogb["row_ids"]]
     absx = np.abs(xf.astype(np.float64))
     cum_abs = compose(ogb, np.abs(x.astype(np.float64)), np.cumsum, np.float64)
+    exact = em.Exact(xf, ogb["offsets"])
+
+    def check_var(name, w, got):
+        """the variance contract against the exact values (tests/exact_moments.py), and the oracle's composition where it is cheap"""
+        T = exact.var(None if name in ("vars", "stddevs") else w)
+        sd = name.startswith("stddev")
+        exact.check(got, T, None if name in ("vars", "stddevs") else w, sd=sd, what=f"{seed} {name} {np.dtype(dt)} w={w} n={n} G={G}")
+        if n * min(max(w, 1), n) <= 3_000_000:
+            op = ck.SCAN_NAMES[name]
+            want = compose(ogb, x, lambda v: oracle.scan(op, v, w), np.float64)
+            b, _ = em.bound(xf, T, None if name in ("vars", "stddevs") else w, ogb["offsets"])
+            tol = np.sqrt(b) if sd else b
+            assert np.all(np.abs(got - want) <= 2 * tol + 1e-9 * np.abs(want)), (seed, name, dt, w, n, G)
+
     for name in rng.choice(SCANS, 3, replace=False):
         op = ck.SCAN_NAMES[str(name)]
         want = compose(ogb, x, lambda v: oracle.scan(op, v), ck.TAG2NP[oracle.scan_out_dtype(op, ck.tag_of(x))])
@@ -97,7 +113,7 @@ def test_grouped_scan_random_shapes(gpu, oracle, seed):
         else:
             assert gu.same_bits(got, want), (seed, name, dt, n, G)
     for name in rng.choice(WINDOWS, 3, replace=False):
-        w = int(rng.choice([1, 2, 3, 5, 10, 64, 100, 1000, 2500, 30_000, n, n + 3]))
+        w = int(rng.choice(FUZZ_W + [n, n + 3]))
         op = ck.SCAN_NAMES[str(name)]
         if name == "avgw" and np.dtype(dt).kind == "u" and np.dtype(dt).itemsize >= 4:
             continue                                          # the reference wraps arr[i] - arr[i-w] for unsigned 4/8-byte inputs
@@ -109,6 +125,13 @@ def test_grouped_scan_random_shapes(gpu, oracle, seed):
             eps_in = float(np.finfo(dt).eps) if fp else 2.0 ** -52
             bound = 4 * eps_in * float(np.max(absx)) * (pos + 2) + 1e-9
             assert np.all(np.abs(got.astype(np.float64) - want.astype(np.float64)) <= bound), (seed, name, dt, w, n, G)
+    # the variance ops on every seed, in addition to the picks above (their own generator: the draws above stay as they were)
+    vrng = np.random.default_rng(int(os.environ.get("AQG_FUZZ_BASE", "9100")) + seed + 1_000_000)
+    for name in ("vars", "stddevs"):
+        check_var(name, 0, gpu.grouped_scan(gb, ck.SCAN_NAMES[name], x))
+    for name in ("varw", "stddevw"):
+        w = int(vrng.choice(FUZZ_W + [n, n + 3]))
+        check_var(name, w, gpu.grouped_scan(gb, ck.SCAN_NAMES[name], x, w))
     # the two-step form (flatten once, scan the flat column) gives the same bits as the one-call form
     xflat = gpu.grouped_flatten(gb, x, keep=True)
     op = ck.SCAN_NAMES["mins"]
