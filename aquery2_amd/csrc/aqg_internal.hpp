@@ -74,6 +74,15 @@ static inline int aqg_fail(aqg_ctx* ctx, int code, const char* msg) {
 #define AQG_CHECK_ROWS(ctx, n, what) do { if ((uint64_t)(n) > (uint64_t)AQG_MAX_ROWS) return aqg_fail(ctx, AQG_ERR_ARG, what ": more than AQG_MAX_ROWS rows"); } while (0)
 static inline uint32_t aqg_ceil_div(uint32_t n, uint32_t d) { return (uint32_t)(((uint64_t)n + d - 1) / d); }
 
+// the environment switches of the README (measurement and test aids), read once per process: the tests start a fresh process to force a plan
+struct aqg_switch_set {
+    uint32_t p1_max, sorted_tail_min;   // AQG_P1_MAX (1024), AQG_SORTED_TAIL_MIN (2^24)
+    int p1_bins;                        // AQG_P1_BINS (0: planned)
+    double pw_sigma;                    // AQG_PW_SIGMA (6)
+    bool disable_p1, disable_p1_cursors, disable_ranged, disable_pw_defer, disable_build_partition, debug_flags, str_host;
+};
+const aqg_switch_set& aqg_switches();
+
 // workspace: reset at the start of an API call, then bump.  Growing synchronises the
 // stream (earlier kernels may still read the old arena) -- call aqg_reserve_workspace
 // ahead of timed regions.

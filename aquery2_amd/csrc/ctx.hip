@@ -238,7 +238,6 @@ int aqg_col_pin(aqg_ctx* ctx, const void* host_ptr, size_t bytes, void** dptr) {
     // every exit below this line releases what the call has locked and allocated so far
     auto fail = [&](int rc) { if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream); pin_release(ctx, pin); (void)hipFree(d); (void)hipGetLastError(); return rc; };
     if (!ctx->copy_stream && hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking) != hipSuccess) { ctx->err = "aqg_col_pin: hipStreamCreateWithFlags failed"; return fail(AQG_ERR_HIP); }
-    static const bool no_register = getenv("AQG_PIN_PAGEABLE") != nullptr;    // A/B measurements only
     constexpr size_t CHUNK = (size_t)256 << 20, PAGE = 4096;
     auto staged = [&](size_t off, size_t len) -> bool {
         constexpr size_t SB = (size_t)32 << 20;
@@ -283,7 +282,7 @@ int aqg_col_pin(aqg_ctx* ctx, const void* host_ptr, size_t bytes, void** dptr) {
         {
             std::lock_guard<std::mutex> lock(g_reg_mu);        // check and register in one step: two GPU threads pinning slices of one array
             locked_by_others = lib_registered(tb, te) || foreign_registered(tb, te);
-            if (!locked_by_others && !no_register && c >= ((size_t)1 << 20) && re > rb) {
+            if (!locked_by_others && c >= ((size_t)1 << 20) && re > rb) {
                 if (hipHostRegister(rb, (size_t)(re - rb), hipHostRegisterDefault) == hipSuccess) {
                     pin.regs.emplace_back(rb, (size_t)(re - rb));
                     g_regs.push_back(RegRange{rb, (size_t)(re - rb)});
@@ -406,6 +405,19 @@ int aqg_last_kernel_ms(aqg_ctx* ctx, float* ms) {
 }
 
 } // extern "C"
+
+// ---- environment switches (aqg_internal.hpp) ----------------------------------------------------
+const aqg_switch_set& aqg_switches() {
+    auto num = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    static const aqg_switch_set s{
+        .p1_max = (uint32_t)num("AQG_P1_MAX", 1024), .sorted_tail_min = (uint32_t)num("AQG_SORTED_TAIL_MIN", 1 << 24), .p1_bins = num("AQG_P1_BINS", 0),
+        .pw_sigma = getenv("AQG_PW_SIGMA") ? atof(getenv("AQG_PW_SIGMA")) : 6.0,
+        .disable_p1 = set("AQG_DISABLE_P1"), .disable_p1_cursors = set("AQG_DISABLE_P1_CURSORS"), .disable_ranged = set("AQG_DISABLE_RANGED"),
+        .disable_pw_defer = set("AQG_DISABLE_PW_DEFER"), .disable_build_partition = set("AQG_DISABLE_BUILD_PARTITION"),
+        .debug_flags = set("AQG_DEBUG_FLAGS"), .str_host = set("AQG_STR_HOST")};
+    return s;
+}
 
 // ---- workspace arena ---------------------------------------------------------------------------
 int aqg_ws_reset(aqg_ctx* ctx) {

@@ -433,8 +433,6 @@ int aqg_dense_aggregate(aqg_ctx* ctx, const KeySpec& ks, const DenseSpec& ds, co
     // key columns all int32 / uint32, at most three of them, at most four accumulators: the register-resident instantiations
     int nk = ks.nkeys <= 3 && as.nacc <= 4 ? ks.nkeys : 0;
     for (int c = 0; c < ks.nkeys; ++c) if (ks.dt[c] != AQG_INT32 && ks.dt[c] != AQG_UINT32) nk = 0;
-    static const bool nk_off = getenv("AQG_DENSE_GENERIC") != nullptr;
-    if (nk_off) nk = 0;
     auto by_nk = [&](auto nacc_tag, auto block_tag) -> int {
         constexpr int N = decltype(nacc_tag)::value, B = decltype(block_tag)::value;
         switch (nk) {

@@ -461,8 +461,7 @@ int exchange_core(aqg_comm* comm, aqg_groupby* L, int nkeys, const int* key_dtyp
     AQG_TRY(allgather(comm, comm->send, comm->recv, bytes));
     // ---- 3'. small exchanges: one merge kernel over the gathered payloads --------------------------------------------------------------
     {
-        static const bool small_off = getenv("AQG_DISABLE_SMALL_MERGE") != nullptr;
-        bool small = !small_off && gmax && nkeys == 1 && nparts >= 0 && nparts <= (int)XS_MAXCOL && (uint64_t)gcap * world <= XS_ROWS && aqg_dtype_size(key_dtypes[0]) <= 8 && !is_fp(key_dtypes[0]);
+        bool small = gmax && nkeys == 1 && nparts >= 0 && nparts <= (int)XS_MAXCOL && (uint64_t)gcap * world <= XS_ROWS && aqg_dtype_size(key_dtypes[0]) <= 8 && !is_fp(key_dtypes[0]);
         SmallMerge sm;
         memset(&sm, 0, sizeof sm);
         int rdt[XS_MAXCOL];

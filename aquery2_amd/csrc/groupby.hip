@@ -1192,102 +1192,170 @@ int make_plan(aqg_ctx* ctx, int naggs, const int* ops, const int* dts, const voi
 struct DenseOut { bool used; DenseSpec spec; };
 constexpr int AQG_ERR_RANGE_MISS = -1001;            // internal: sampled key ranges missed a value; run_with_retry repeats the attempt      // tells aqg_groupby_build that the table is the direct-indexed one
 
-int run_agg(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint32_t n, uint32_t hint, bool for_build, aqg_groupby* h,
-            GTable* gt_out, uint32_t** slot_gid_out, uint32_t** occ_out = nullptr, DenseOut* dense_out = nullptr) {
+// LDS mode, small: one workgroup's table (75 % load) fits 64 KB, several workgroups per CU.
+// LDS mode, big:   one 1024-thread workgroup per CU with a table of up to 150 KB, and up to MAX_PASSES passes over the
+//                  rows, each aggregating the keys of one hash class (agg_kernel).  Beyond that rows go straight to HBM.
+constexpr uint32_t MAX_PASSES = 4;
+constexpr size_t LDS_SMALL = 76 * 1024, LDS_BIG = 150 * 1024;      // small: two workgroups per CU still fit
+// LDS table of one round-1 partition: as many slots as fit the budget (the slot of a hash is a multiply-shift, so the capacity need not
+// be a power of two).  Partitions are sized for a LOW load factor: probe sequences are walked by whole wavefronts, and measured at 1e9
+// rows / 1e7 groups the LDS aggregation takes 3.9 ms at load 0.20, 5.6 ms at 0.22-0.25, 6.7-7.2 ms at 0.30-0.33 and 18 ms at 0.6 (two
+// accumulators), while one more partition bit costs the two scatter passes 1-2 ms.
+constexpr size_t PART_LDS_BYTES = 60 * 1024;
+constexpr uint64_t PART_LF1000 = 210;
+// (one lane per bitmap word of a 16384-row interval: 512 at least)
+constexpr unsigned SORTED_EMIT_BLOCK = 1024;
+
+// the row pass of an attempt
+enum class RowPass { STARJOIN, FAST_LDS, DENSE, PART_WIDE, PART_ONE, PART_TWO, PART_ROUND1, HASHED };
+
+// every decision of one attempt (make_agg_plan)
+struct AggPlan {
+    uint32_t n, hint;                 // hint: a tiny dense domain replaces the caller's
+    bool for_build, k32;              // k32: one 4-byte key column
+    KeySpec ks;                       // packed keys of many expected groups are promoted to wide tuples
+    Plan plan;                        // the partitioned build also counts the groups
+    bool use_lds, big_lds, dense, build_part, use_part, lookup_build, use_wpart, rows_possible, sorted_tail, small_rank, sparse_rank, ordered_emit;
+    bool fast, fast_k64, fast_key8, fast_v8, defer;      // defer: the flags are judged behind the queued tail (fast path and star join, small tables)
+    uint32_t lcap, npass, lk_min, lk_D, pbits, part_lcap, p1_bins, p2_parts, gcap, nwords, ntiles;
+    int part_layout;
+    size_t lds_slot_bytes;
+    uint64_t lds_group_cap;
+    DenseSpec dspec;
+    FastVals fv;
+    RowPass pass;
+};
+
+// the attempt's buffers, carved from the workspace arena in a fixed order (timings depend on where they land)
+struct AggBufs {
+    GTable gt;
+    size_t slots;
+    uint32_t *occ, *gid_of_occ, *slot_gid, *bitmap, *word_prefix, *tile_total, *tile_mark, *pinned_flags;   // pinned_flags: defer's copy of the flag words
+    PartRows prows;
+};
+
+// dense key domain (dense.hip): direct-indexed tables when the product of the key columns' value ranges is small --
+// also for tuples wider than 64 bits.  Costs one more pass over the key columns, so it is only tried where the
+// alternatives are the multi-pass hashed table or the partition pipeline.
+int plan_dense(aqg_ctx* ctx, aqg_groupby* h, AggPlan& p) {
+    const KeySpec& ks = p.ks;
+    long long mins[MAXKEYS], maxs[MAXKEYS];
+    bool ok = false;
+    AQG_TRY(aqg_ws_reset(ctx));
+    AQG_TRY(aqg_ws_ensure(ctx, 4096));
+    // large inputs: ranges from the first 2^20 rows (a full pass over the key columns costs a third of Q2); the kernels check
+    // every row against them and flag a miss, which re-runs the call once with exact ranges (and remembers it in the handle)
+    const bool sampled = p.n >= (1u << 22) && !h->dense_exact;
+    bool cached = sampled && h->range_valid && h->range_nkeys == ks.nkeys && h->range_n == p.n;
+    for (int c = 0; c < ks.nkeys && cached; ++c) cached = h->range_col[c] == ks.col[c] && h->range_dt[c] == ks.dt[c];
+    if (cached) { for (int c = 0; c < ks.nkeys; ++c) { mins[c] = h->range_min[c]; maxs[c] = h->range_max[c]; } ok = true; }
+    else {
+        AQG_TRY(aqg_key_ranges(ctx, ks, sampled ? (1u << 20) : p.n, mins, maxs, &ok, sampled ? p.n : 0u));
+        h->range_valid = sampled && ok;
+        if (h->range_valid) {
+            h->range_nkeys = ks.nkeys; h->range_n = p.n;
+            for (int c = 0; c < ks.nkeys; ++c) { h->range_col[c] = ks.col[c]; h->range_dt[c] = ks.dt[c]; h->range_min[c] = mins[c]; h->range_max[c] = maxs[c]; }
+        }
+    }
+    p.dense = ok && aqg_dense_plan(ks, mins, maxs, p.plan.as, p.plan.need_count, &p.dspec);
+    p.dspec.sampled = sampled;
+    if (p.dense && p.dspec.D <= 1536) {          // (ranges from a sample are fine here: the hashed table takes any key)
+        // a tiny domain under a large hint: the small hashed table after all (1024 lanes on a hundred hot direct-indexed
+        // slots serialise on LDS atomics: 6.2 ms per 1e9 rows against 2.7 ms)
+        const uint32_t small_cap = next_pow2((uint64_t)(p.dspec.D < 64 ? 64 : p.dspec.D) * 4 / 3 + 1);
+        if ((size_t)(small_cap + 1) * p.lds_slot_bytes <= LDS_SMALL) { p.dense = false; p.use_lds = true; p.lcap = small_cap < 256 ? 256 : small_cap; p.hint = p.dspec.D; }
+    }
+    if (p.dense) p.gcap = p.dspec.D;
+    return AQG_OK;
+}
+
+// fast path eligibility: LDS mode, 16-byte aligned columns, one or two 4-byte integer keys or one 8-byte key, up to four accumulators
+// of any kind over integer / floating value columns (also the first pass of aqg_groupby_build: no accumulators, only the distinct keys)
+void plan_fast(AggPlan& p) {
+    const KeySpec& ks = p.ks;
+    const AccSpec& as = p.plan.as;
+    auto key32 = [&](int j) { return (ks.dt[j] == AQG_INT32 || ks.dt[j] == AQG_UINT32) && ((uintptr_t)ks.col[j] & 15) == 0; };
+    // two 4-byte key columns, or one 8-byte key column whose bits are the packed key
+    p.fast_key8 = ks.nkeys == 1 && !ks.wide && (ks.dt[0] == AQG_INT64 || ks.dt[0] == AQG_UINT64) && ((uintptr_t)ks.col[0] & 15) == 0;
+    p.fast_k64 = (ks.nkeys == 2 && !ks.wide && ks.total_bytes == 8 && key32(0) && key32(1)) || p.fast_key8;
+    p.fast = p.use_lds && !p.plan.sj && !p.big_lds && ((p.k32 && key32(0)) || p.fast_k64) && p.n >= 8 && (as.nacc >= 1 || p.plan.need_count || p.for_build) && as.nacc <= 4;
+    // value columns: 4 bytes wide, or 4 and 8 bytes wide (an int64 sum takes two accumulators)
+    auto wide_dt = [](int dt) { return dt == AQG_INT64 || dt == AQG_UINT64 || dt == AQG_DOUBLE; };
+    auto narrow_dt = [](int dt) { return dt == AQG_INT32 || dt == AQG_UINT32 || dt == AQG_FLOAT; };
+    auto tiny_dt = [](int dt) { return dt == AQG_INT8 || dt == AQG_UINT8 || dt == AQG_BOOL || dt == AQG_INT16 || dt == AQG_UINT16; };
+    // some value column is 1, 2 or 8 bytes wide: the VW = 8 instantiation (it takes 4-byte ones, too)
+    for (int a = 0; a < as.nacc; ++a) p.fast_v8 = p.fast_v8 || wide_dt(as.dt[a]) || tiny_dt(as.dt[a]);
+    FastVals& fv = p.fv;
+    for (int a = 0; a < as.nacc && p.fast; ++a) {
+        const int dt = as.dt[a];
+        if ((uintptr_t)as.col[a] & 15) p.fast = false;
+        if (p.fast_v8) { if (!wide_dt(dt) && !narrow_dt(dt) && !tiny_dt(dt)) p.fast = false; }
+        else if (as.part[a] || !narrow_dt(dt)) p.fast = false;
+        fv.col[a] = as.col[a];
+        fv.vkind[a] = dt == AQG_INT32 ? 0 : dt == AQG_UINT32 ? 1 : dt == AQG_FLOAT ? 2 : dt == AQG_INT64 ? 3 : dt == AQG_UINT64 ? 4 : dt == AQG_DOUBLE ? 5 :
+                      dt == AQG_INT8 ? 6 : (dt == AQG_UINT8 || dt == AQG_BOOL) ? 7 : dt == AQG_INT16 ? 8 : 9;
+        fv.kind[a] = as.kind[a];
+        fv.square[a] = as.square[a];
+        fv.part[a] = as.part[a];
+    }
+}
+
+// Every decision of one attempt, with the device sampling they need (dense key ranges, the look-up build's domain).
+// table_out: the caller takes the group table itself; dense_out: the caller takes a direct-indexed table
+int make_agg_plan(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint32_t n, uint32_t hint, bool for_build, bool table_out, bool dense_out,
+                  aqg_groupby* h, AggPlan* out) {
+    const aqg_switch_set& sw = aqg_switches();
+    AggPlan& p = *out;
+    p = AggPlan{};
+    p.n = n; p.for_build = for_build; p.ks = ks_in; p.plan = plan_in; p.hint = hint;
+    KeySpec& ks = p.ks;
+    const AccSpec& as = p.plan.as;
     // Packed keys (<= 8 bytes) with more groups expected than their partition plans reach (2^25) are handled as WIDE tuples: that plan
     // partitions on a hash of the tuple and compares tuples through representative rows, whatever the key width, up to one group per row
     // (2e8 unique 4-byte keys: 107 ms through the HBM table of scattered device atomics they fell to before)
-    KeySpec ks = ks_in;
-    static const bool widen_off = getenv("AQG_DISABLE_WIDEN_PACKED") != nullptr;      // A/B measurements only
-    if (!widen_off && !ks.wide && !for_build && hint > (1u << 25) && n >= (1u << 20) && !plan_in.sj && plan_in.as.nacc <= 4) {
+    if (!ks.wide && !for_build && hint > (1u << 25) && n >= (1u << 20) && !p.plan.sj && as.nacc <= 4) {
         ks.wide = 1;
         for (int j = 0; j < ks.nkeys; ++j) ks.shift[j] = 0;
     }
-    // more than ~1.6e7 groups expected out of a partition plan: the records are ORDERED (aqg_sorted_tail) instead of ranked through a
-    // bitmap over the rows and gathered (h2o Q10, 1e9 groups: that tail took 219 of 317 ms and fetched 900 GB)
-    static const uint32_t sorted_min = getenv("AQG_SORTED_TAIL_MIN") ? (uint32_t)atoi(getenv("AQG_SORTED_TAIL_MIN")) : (1u << 24);
     // A BUILD above the LDS tables takes the partition plans too (partition1.hip: the group table with counts, then one more pass over the
     // partitioned rows for the id of every row) instead of inserting every row into an HBM table and looking every row up again
-    static const bool build_part_off = getenv("AQG_DISABLE_BUILD_PARTITION") != nullptr;     // A/B measurements only
-    const bool build_part = for_build && !build_part_off && !ks.wide && n >= (1u << 20) && hint > 3072 && hint <= (1u << 25) && hint < sorted_min;
-    Plan plan = plan_in;
-    if (build_part) plan.need_count = 1;          // the group sizes come out of the partition aggregation
-    const AccSpec& as = plan.as;
-    const bool k32 = ks.nkeys == 1 && ks.total_bytes == 4;
-    uint32_t gcap = next_pow2((uint64_t)(hint < 512 ? 512 : hint) * 2);
-    // LDS mode, small: one workgroup's table (75 % load) fits 64 KB, several workgroups per CU.
-    // LDS mode, big:   one 1024-thread workgroup per CU with a table of up to 150 KB, and up to MAX_PASSES passes over the
-    //                  rows, each aggregating the keys of one hash class (agg_kernel).  Beyond that rows go straight to HBM.
-    constexpr uint32_t MAX_PASSES = 4;
-    constexpr size_t LDS_SMALL = 76 * 1024, LDS_BIG = 150 * 1024;      // small: two workgroups per CU still fit
-    bool use_lds = hint <= 3072 && !ks.wide;   // wide tuples compare against HBM-resident rows: HBM mode
-    uint32_t lcap = use_lds ? next_pow2((uint64_t)(hint < 64 ? 64 : hint) * 4 / 3 + 1) : 0;
-    if (use_lds && lcap < 256) lcap = 256;
-    const size_t lds_slot_bytes = 8 + 8 * (size_t)as.nacc + (k32 ? 0 : 4) + (plan.need_count ? 4 : 0);
-    if (use_lds && (size_t)(lcap + 1) * lds_slot_bytes > LDS_SMALL) { use_lds = false; lcap = 0; }
-    if (plan.sj && !(use_lds && k32))
+    p.build_part = for_build && !sw.disable_build_partition && !ks.wide && n >= (1u << 20) && hint > 3072 && hint <= (1u << 25) && hint < sw.sorted_tail_min;
+    if (p.build_part) p.plan.need_count = 1;          // the group sizes come out of the partition aggregation
+    p.k32 = ks.nkeys == 1 && ks.total_bytes == 4;
+    p.gcap = next_pow2((uint64_t)(hint < 512 ? 512 : hint) * 2);
+    p.use_lds = hint <= 3072 && !ks.wide;   // wide tuples compare against HBM-resident rows: HBM mode
+    p.lcap = p.use_lds ? next_pow2((uint64_t)(hint < 64 ? 64 : hint) * 4 / 3 + 1) : 0;
+    if (p.use_lds && p.lcap < 256) p.lcap = 256;
+    p.lds_slot_bytes = 8 + 8 * (size_t)as.nacc + (p.k32 ? 0 : 4) + (p.plan.need_count ? 4 : 0);
+    if (p.use_lds && (size_t)(p.lcap + 1) * p.lds_slot_bytes > LDS_SMALL) { p.use_lds = false; p.lcap = 0; }
+    if (p.plan.sj && !(p.use_lds && p.k32))
         return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_groupby_sum: needs one 4-byte group key and at most 3072 groups (compose aqg_join_lookup / aqg_gather / aqg_ewise / aqg_groupby_agg beyond that)");
-    uint32_t npass = 1;
-    bool big_lds = false;
-    // dense key domain (dense.hip): direct-indexed tables when the product of the key columns' value ranges is small --
-    // also for tuples wider than 64 bits.  Costs one more pass over the key columns, so it is only tried where the
-    // alternatives are the multi-pass hashed table or the partition pipeline.
-    bool dense = false;
-    DenseSpec dspec;
-    static const bool dense_off = getenv("AQG_DISABLE_DENSE") != nullptr;    // A/B measurements only
-    if (!dense_off && !plan.sj && !use_lds && (!for_build || dense_out) && n >= (1u << 20) &&
-        (uint64_t)hint <= (uint64_t)(DENSE_LDS_BYTES / aqg_dense_slot_bytes(as, plan.need_count)) * DENSE_MAX_PASSES) {
-        long long mins[MAXKEYS], maxs[MAXKEYS];
-        bool ok = false;
-        AQG_TRY(aqg_ws_reset(ctx));
-        AQG_TRY(aqg_ws_ensure(ctx, 4096));
-        // large inputs: ranges from the first 2^20 rows (a full pass over the key columns costs a third of Q2); the kernels check
-        // every row against them and flag a miss, which re-runs the call once with exact ranges (and remembers it in the handle)
-        const bool sampled = n >= (1u << 22) && !h->dense_exact;
-        bool cached = sampled && h->range_valid && h->range_nkeys == ks.nkeys && h->range_n == n;
-        for (int c = 0; c < ks.nkeys && cached; ++c) cached = h->range_col[c] == ks.col[c] && h->range_dt[c] == ks.dt[c];
-        if (cached) { for (int c = 0; c < ks.nkeys; ++c) { mins[c] = h->range_min[c]; maxs[c] = h->range_max[c]; } ok = true; }
-        else {
-            AQG_TRY(aqg_key_ranges(ctx, ks, sampled ? (1u << 20) : n, mins, maxs, &ok, sampled ? n : 0u));
-            h->range_valid = sampled && ok;
-            if (h->range_valid) {
-                h->range_nkeys = ks.nkeys; h->range_n = n;
-                for (int c = 0; c < ks.nkeys; ++c) { h->range_col[c] = ks.col[c]; h->range_dt[c] = ks.dt[c]; h->range_min[c] = mins[c]; h->range_max[c] = maxs[c]; }
-            }
-        }
-        dense = ok && aqg_dense_plan(ks, mins, maxs, as, plan.need_count, &dspec);
-        dspec.sampled = sampled;
-        if (dense && dspec.D <= 1536) {          // (ranges from a sample are fine here: the hashed table takes any key)
-            // a tiny domain under a large hint: the small hashed table after all (1024 lanes on a hundred hot direct-indexed
-            // slots serialise on LDS atomics: 6.2 ms per 1e9 rows against 2.7 ms)
-            const uint32_t small_cap = next_pow2((uint64_t)(dspec.D < 64 ? 64 : dspec.D) * 4 / 3 + 1);
-            if ((size_t)(small_cap + 1) * lds_slot_bytes <= LDS_SMALL) { dense = false; use_lds = true; lcap = small_cap < 256 ? 256 : small_cap; hint = dspec.D; }
-        }
-        if (dense) gcap = dspec.D;
-    }
-    if (!dense && !use_lds && !ks.wide && n >= (1u << 20)) {
-        const uint32_t max_slots = (uint32_t)(LDS_BIG / lds_slot_bytes) - 1;
+    p.npass = 1;
+    if (!p.plan.sj && !p.use_lds && (!for_build || dense_out) && n >= (1u << 20) &&
+        (uint64_t)hint <= (uint64_t)(DENSE_LDS_BYTES / aqg_dense_slot_bytes(as, p.plan.need_count)) * DENSE_MAX_PASSES)
+        AQG_TRY(plan_dense(ctx, h, p));
+    hint = p.hint;                                    // (from here on the effective hint)
+    if (!p.dense && !p.use_lds && !ks.wide && n >= (1u << 20)) {
+        const uint32_t max_slots = (uint32_t)(LDS_BIG / p.lds_slot_bytes) - 1;
         const uint32_t per_pass = max_slots - (max_slots >> 2);
         const uint64_t want = ((uint64_t)hint + per_pass - 1) / per_pass;
-        if (want <= MAX_PASSES) { use_lds = big_lds = true; npass = (uint32_t)want; lcap = max_slots; }
+        if (want <= MAX_PASSES) { p.use_lds = p.big_lds = true; p.npass = (uint32_t)want; p.lcap = max_slots; }
     }
-    const uint64_t lds_group_cap = use_lds ? (uint64_t)npass * (lcap - (lcap >> 2)) : 0;
-    const bool small_rank = hint <= 4096;
-    const uint32_t nwords = aqg_ceil_div(n, 32), ntiles = aqg_ceil_div(nwords, 1024);
+    p.lds_group_cap = p.use_lds ? (uint64_t)p.npass * (p.lcap - (p.lcap >> 2)) : 0;
+    p.small_rank = hint <= 4096;
+    p.nwords = aqg_ceil_div(n, 32); p.ntiles = aqg_ceil_div(p.nwords, 1024);
     // groups beyond the LDS tables: partition the rows instead of hammering an HBM table with scattered atomics
     // (partition.hip: h2o Q5, 1e9 rows, 1e7 groups: 42 ms against 141 ms); the build path keeps the HBM table because
-    // its second pass looks keys up in it.  AQG_DISABLE_PARTITION=1 forces the HBM table (A/B measurements only).
-    static const bool part_off = getenv("AQG_DISABLE_PARTITION") != nullptr;
-    bool use_part = !part_off && !dense && !use_lds && !ks.wide && (!for_build || build_part) && n >= (1u << 20) && hint <= (1u << 25);
-    if (use_part && for_build) {                  // (the build's id pass knows the one- and two-level plans only)
-        const uint32_t bp = aqg_partition_parts(ks.total_bytes <= 4 ? 4 : 8, as, plan.need_count, hint);
-        if (!bp || bp > AQG_P2_MAXPARTS) use_part = false;
+    // its second pass looks keys up in it
+    const int ksz = ks.total_bytes <= 4 ? 4 : 8;
+    const uint32_t record_cap = (uint32_t)((uint64_t)hint + hint / 4 + 4096 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : (uint64_t)hint + hint / 4 + 4096);   // compact record table
+    p.use_part = !p.dense && !p.use_lds && !ks.wide && (!for_build || p.build_part) && n >= (1u << 20) && hint <= (1u << 25);
+    if (p.use_part && for_build) {                  // (the build's id pass knows the one- and two-level plans only)
+        const uint32_t bp = aqg_partition_parts(ksz, as, p.plan.need_count, hint);
+        if (!bp || bp > AQG_P2_MAXPARTS) p.use_part = false;
     }
     // the build over a dense key domain small enough for a key -> id look-up table (lookup_assign_kernel): no partitioned rows kept, no routing
-    bool lookup_build = false;
-    uint32_t lk_min = 0, lk_D = 0;
-    static const bool lookup_off = getenv("AQG_DISABLE_LOOKUP_BUILD") != nullptr;     // A/B measurements only
-    if (use_part && for_build && !lookup_off && !h->no_lookup_build && ks.nkeys == 1 && !ks.wide && (ks.dt[0] == AQG_INT32 || ks.dt[0] == AQG_UINT32) &&
+    if (p.use_part && for_build && !h->no_lookup_build && ks.nkeys == 1 && (ks.dt[0] == AQG_INT32 || ks.dt[0] == AQG_UINT32) &&
         ((uintptr_t)ks.col[0] & 15) == 0 && n >= (1u << 22)) {
         long long mn[MAXKEYS], mx[MAXKEYS];
         bool ok = false;
@@ -1296,318 +1364,302 @@ int run_agg(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint32_t n,
         AQG_TRY(aqg_key_ranges(ctx, ks, 1u << 20, mn, mx, &ok, n));         // (a sample spread over the column: the look-up pass checks every row)
         if (ok && mx[0] >= mn[0]) {
             const long long span = mx[0] - mn[0] + 1, room = span / 64 + 1024, lo = mn[0] - room, hi = mx[0] + room;
-            if (hi - lo + 1 <= (1ll << 21)) { lookup_build = true; lk_min = (uint32_t)lo; lk_D = (uint32_t)(hi - lo + 1); }
+            if (hi - lo + 1 <= (1ll << 21)) { p.lookup_build = true; p.lk_min = (uint32_t)lo; p.lk_D = (uint32_t)(hi - lo + 1); }
         }
     }
-    uint32_t part_lcap = 0, pbits = 0;
-    if (use_part) {
-        // LDS table of one partition: as many slots as fit the budget (the slot of a hash is a multiply-shift, so the
-        // capacity need not be a power of two).  Partitions are sized for a LOW load factor: probe sequences are walked by
-        // whole wavefronts, and measured at 1e9 rows / 1e7 groups the LDS aggregation takes 3.9 ms at load 0.20, 5.6 ms at
-        // 0.22-0.25, 6.7-7.2 ms at 0.30-0.33 and 18 ms at 0.6 (two accumulators), while one more partition bit costs the two
-        // scatter passes 1-2 ms.  AQG_PART_LF1000 / AQG_PART_LDSKB / AQG_PART_LCAP: measurement switches.
-        static const int lf1000 = getenv("AQG_PART_LF1000") ? atoi(getenv("AQG_PART_LF1000")) : 210;
-        static const int lds_kb = getenv("AQG_PART_LDSKB") ? atoi(getenv("AQG_PART_LDSKB")) : 60;
-        const size_t sb = 16 + 8 * (size_t)as.nacc;
-        part_lcap = (uint32_t)((size_t)lds_kb * 1024 / sb) - 1;
-        { static const int lcap_env = getenv("AQG_PART_LCAP") ? atoi(getenv("AQG_PART_LCAP")) : 0; if (lcap_env > 0) part_lcap = (uint32_t)lcap_env; }
-        pbits = 10;                                  // at least 1024 partitions: every CU gets several
-        while (pbits < 16 && ((uint64_t)hint >> pbits) * 1000 > (uint64_t)part_lcap * lf1000) ++pbits;
-        gcap = (uint32_t)((uint64_t)hint + hint / 4 + 4096 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : (uint64_t)hint + hint / 4 + 4096);   // compact record table
+    if (p.use_part) {
+        p.part_lcap = (uint32_t)(PART_LDS_BYTES / (16 + 8 * (size_t)as.nacc)) - 1;
+        p.pbits = 10;                                  // at least 1024 partitions: every CU gets several
+        while (p.pbits < 16 && ((uint64_t)hint >> p.pbits) * 1000 > (uint64_t)p.part_lcap * PART_LF1000) ++p.pbits;
+        p.gcap = record_cap;
     }
     // partition1.hip: ONE level up to ~1000 partitions (every plane moves once), two levels of <= 64 bins up to 4096 (the runs a
     // tile writes stay a kilobyte long); beyond that the round-1 pipeline of partition.hip
-    static const bool p1_off_env = getenv("AQG_DISABLE_P1") != nullptr;      // A/B measurements only
-    const bool p1_off = p1_off_env && !for_build;
-    static const uint32_t p1_max = getenv("AQG_P1_MAX") ? (uint32_t)atoi(getenv("AQG_P1_MAX")) : 1024u;
-    int part_layout = AQG_P1_LAYOUT_DENSE_IDS;
-    const uint32_t parts = use_part && !p1_off ? aqg_partition_parts(ks.total_bytes <= 4 ? 4 : 8, as, plan.need_count, hint, &part_layout) : 0;
-    const uint32_t p1_bins = parts && parts <= p1_max && parts <= AQG_P1_MAXBINS ? parts : 0;
-    const uint32_t p2_parts = parts && !p1_bins && parts <= AQG_P2_MAXPARTS ? parts : 0;
+    const bool p1_off = sw.disable_p1 && !for_build;
+    p.part_layout = AQG_P1_LAYOUT_DENSE_IDS;
+    const uint32_t parts = p.use_part && !p1_off ? aqg_partition_parts(ksz, as, p.plan.need_count, hint, &p.part_layout) : 0;
+    p.p1_bins = parts && parts <= sw.p1_max && parts <= AQG_P1_MAXBINS ? parts : 0;
+    p.p2_parts = parts && !p.p1_bins && parts <= AQG_P2_MAXPARTS ? parts : 0;
+    // every row its own group out of a partition plan: the result can be written from the input rows (emit_rows_kernel) -- when nobody asks for the table itself
+    p.rows_possible = n >= (1u << 16) && !for_build && !p.plan.sj && !table_out;
     // tuples wider than 8 bytes with many groups (h2o Q10): hash-partitioned rows, every partition grouped inside LDS
-    // every row its own group out of a partition plan: the result can be written from the input rows (emit_rows_kernel below) -- when nobody asks for the table itself
-    static const bool rows_off = getenv("AQG_DISABLE_ROW_EMIT") != nullptr;                 // A/B measurements only
-    const bool rows_possible = !rows_off && n >= (1u << 16) && !for_build && !plan.sj && !gt_out && !slot_gid_out && !occ_out;
-    const bool use_wpart = !part_off && !p1_off && !dense && !use_lds && ks.wide && !for_build && !plan.sj && n >= (1u << 20) && hint > (1u << 20) && as.nacc <= 4 &&
-                           !h->no_wide_part && aqg_partitionw_applies(ks, as, n, hint);
-    if (use_wpart) gcap = (uint32_t)((uint64_t)hint + hint / 4 + 4096 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : (uint64_t)hint + hint / 4 + 4096);
+    p.use_wpart = !p1_off && !p.dense && !p.use_lds && ks.wide && !for_build && !p.plan.sj && n >= (1u << 20) && hint > (1u << 20) && as.nacc <= 4 &&
+                  !h->no_wide_part && aqg_partitionw_applies(ks, as, n, hint);
+    if (p.use_wpart) p.gcap = record_cap;
+    // more than ~1.6e7 groups expected out of a partition plan: the records are ORDERED (aqg_sorted_tail) instead of ranked through a
+    // bitmap over the rows and gathered (h2o Q10, 1e9 groups: that tail took 219 of 317 ms and fetched 900 GB)
+    p.sorted_tail = (p.use_part || p.use_wpart) && !for_build && hint >= sw.sorted_tail_min && !h->no_sorted_tail && aqg_sorted_tail_plan(n, as.nacc, ks.wide != 0, nullptr);
+    p.ordered_emit = !p.small_rank && hint >= (1u << 20) && !p.sorted_tail;
+    // few groups over many rows: the context's all-zero bitmap, only the tiles that hold a bit are scanned (bitmap_set_kernel)
+    p.sparse_rank = !p.small_rank && !p.sorted_tail && p.nwords >= (1u << 16) && (uint64_t)hint * 64 < p.nwords;
+    plan_fast(p);
+    p.pass = p.plan.sj ? RowPass::STARJOIN : p.fast ? RowPass::FAST_LDS : p.dense ? RowPass::DENSE : p.use_wpart ? RowPass::PART_WIDE :
+             p.p1_bins ? RowPass::PART_ONE : p.p2_parts ? RowPass::PART_TWO : p.use_part ? RowPass::PART_ROUND1 : RowPass::HASHED;
+    p.defer = n && (p.pass == RowPass::FAST_LDS || p.pass == RowPass::STARJOIN) && p.small_rank;
+    return AQG_OK;
+}
 
-    const bool sorted_tail = (use_part || use_wpart) && !for_build && hint >= sorted_min && !h->no_sorted_tail && aqg_sorted_tail_plan(n, as.nacc, ks.wide != 0, nullptr);
-    // ---- workspace ----------------------------------------------------------------------------
-    size_t slots = (size_t)gcap + 1;
+// the workspace of an attempt: the group table, the ids of its occupied slots, the ranking bitmap, the partition or ordering buffers
+int agg_workspace(aqg_ctx* ctx, const AggPlan& p, AggBufs* out) {
+    const KeySpec& ks = p.ks;
+    const AccSpec& as = p.plan.as;
+    AggBufs& b = *out;
+    b = AggBufs{};
+    const size_t slots = b.slots = (size_t)p.gcap + 1;
     uint32_t stride = 16;
     while (stride < 16 + 8 * (uint32_t)as.nacc) stride <<= 1;
     size_t need = slots * (size_t)stride + 4096 + 256 * 16;
-    if (!sorted_tail) need += slots * (4 + 4 + 4);
-    if (!small_rank && !sorted_tail) need += (size_t)nwords * 8 + (size_t)ntiles * 8 + 8192;
-    const bool ordered_emit = !small_rank && hint >= (1u << 20) && !sorted_tail;
-    if (ordered_emit) need += slots * 4 + 4096;
+    if (!p.sorted_tail) need += slots * (4 + 4 + 4);
+    if (!p.small_rank && !p.sorted_tail) need += (size_t)p.nwords * 8 + (size_t)p.ntiles * 8 + 8192;
+    if (p.ordered_emit) need += slots * 4 + 4096;
     size_t part_need = 0;
-    if (use_wpart) part_need = aqg_partitionw_ws_bytes(ctx, ks, n, as, hint) + 65536;
-    else if (p1_bins) part_need = aqg_partition1_ws_bytes(ctx, ks, n, as, p1_bins) + 65536;
-    else if (p2_parts) part_need = aqg_partition2_ws_bytes(ctx, ks, n, as, p2_parts) + 65536;
-    else if (use_part) part_need = aqg_partition_ws_bytes(n, ks.total_bytes <= 4 ? 4 : 8, as, pbits) + 65536;
+    if (p.use_wpart) part_need = aqg_partitionw_ws_bytes(ctx, ks, p.n, as, p.hint) + 65536;
+    else if (p.p1_bins) part_need = aqg_partition1_ws_bytes(ctx, ks, p.n, as, p.p1_bins) + 65536;
+    else if (p.p2_parts) part_need = aqg_partition2_ws_bytes(ctx, ks, p.n, as, p.p2_parts) + 65536;
+    else if (p.use_part) part_need = aqg_partition_ws_bytes(p.n, ks.total_bytes <= 4 ? 4 : 8, as, p.pbits) + 65536;
     // (the partition buffers are dead once the record table is written: the ordering pass takes their place in the arena)
-    const size_t sort_need = sorted_tail ? aqg_sorted_tail_ws_bytes(gcap, n, as.nacc, ks.wide != 0) : 0;
+    const size_t sort_need = p.sorted_tail ? aqg_sorted_tail_ws_bytes(p.gcap, p.n, as.nacc, ks.wide != 0) : 0;
     need += part_need > sort_need ? part_need : sort_need;
-    if (for_build && use_part) need += lookup_build ? ((size_t)lk_D + 64) * 4 + 4096 : aqg_partition_assign_ws_bytes(n);
+    if (p.for_build && p.use_part) need += p.lookup_build ? ((size_t)p.lk_D + 64) * 4 + 4096 : aqg_partition_assign_ws_bytes(p.n);
     AQG_TRY(aqg_ws_reset(ctx));
     AQG_TRY(aqg_ws_ensure(ctx, need));
-    GTable gt;
-    memset(&gt, 0, sizeof gt);
-    gt.cap = gcap;
-    gt.has_count = plan.need_count;
-    PartRows prows;
-    memset(&prows, 0, sizeof prows);
-    uint32_t *occ, *gid_of_occ, *slot_gid, *bitmap = nullptr, *word_prefix = nullptr, *tile_total = nullptr;
-    {
-        unsigned char* base = nullptr;
-        AQG_TRY(aqg_ws_get(ctx, slots * stride, &base));
-        const bool records = (use_part || use_wpart || hint > (1u << 17)) && !sorted_tail;   // (the ordering pass moves column planes)
-        if (records) {
-            gt.kb = base; gt.fb = base + 8; gt.cb = base + 12; gt.ab = base + 16;
-            gt.kst = gt.fst = gt.cst = gt.ast = stride; gt.astep = 8;
-        } else {
-            gt.kb = base; gt.fb = base + slots * 8; gt.cb = gt.fb + slots * 4; gt.ab = gt.cb + slots * 4;
-            gt.kst = 8; gt.fst = 4; gt.cst = 4; gt.ast = 8; gt.astep = (uint64_t)slots * 8;
-        }
+    GTable& gt = b.gt;
+    gt.cap = p.gcap;
+    gt.has_count = p.plan.need_count;
+    unsigned char* base = nullptr;
+    AQG_TRY(aqg_ws_get(ctx, slots * stride, &base));
+    const bool records = (p.use_part || p.use_wpart || p.hint > (1u << 17)) && !p.sorted_tail;   // (the ordering pass moves column planes)
+    if (records) {
+        gt.kb = base; gt.fb = base + 8; gt.cb = base + 12; gt.ab = base + 16;
+        gt.kst = gt.fst = gt.cst = gt.ast = stride; gt.astep = 8;
+    } else {
+        gt.kb = base; gt.fb = base + slots * 8; gt.cb = gt.fb + slots * 4; gt.ab = gt.cb + slots * 4;
+        gt.kst = 8; gt.fst = 4; gt.cst = 4; gt.ast = 8; gt.astep = (uint64_t)slots * 8;
     }
     AQG_TRY(aqg_ws_get(ctx, 64, &gt.flags));
-    if (sorted_tail && use_wpart) gt.kb = nullptr;       // wide tuples through the ordering tail: the key word would repeat the first-row plane
-    occ = gid_of_occ = slot_gid = nullptr;
-    if (!sorted_tail) {
-        AQG_TRY(aqg_ws_get(ctx, slots, &occ));
-        AQG_TRY(aqg_ws_get(ctx, slots, &gid_of_occ));
-        AQG_TRY(aqg_ws_get(ctx, slots, &slot_gid));
+    if (p.sorted_tail && p.use_wpart) gt.kb = nullptr;       // wide tuples through the ordering tail: the key word would repeat the first-row plane
+    if (!p.sorted_tail) {
+        AQG_TRY(aqg_ws_get(ctx, slots, &b.occ));
+        AQG_TRY(aqg_ws_get(ctx, slots, &b.gid_of_occ));
+        AQG_TRY(aqg_ws_get(ctx, slots, &b.slot_gid));
     }
-    // few groups over many rows: the context's all-zero bitmap, only the tiles that hold a bit are scanned (bitmap_set_kernel)
-    static const bool sparse_off = getenv("AQG_DISABLE_SPARSE_RANK") != nullptr;
-    const bool sparse_rank = !small_rank && !sorted_tail && !sparse_off && nwords >= (1u << 16) && (uint64_t)hint * 64 < nwords;
-    uint32_t* tile_mark = nullptr;
-    if (!small_rank && !sorted_tail) {
-        if (sparse_rank) {
-            if (ctx->rank_bm_words < nwords) {
+    if (!p.small_rank && !p.sorted_tail) {
+        if (p.sparse_rank) {
+            if (ctx->rank_bm_words < p.nwords) {
                 if (ctx->rank_bm) { AQG_HIP(ctx, hipStreamSynchronize(ctx->stream)); AQG_HIP(ctx, hipFree(ctx->rank_bm)); ctx->rank_bm = nullptr; ctx->rank_bm_words = 0; }
-                if (hipMalloc(&ctx->rank_bm, (size_t)nwords * 4) != hipSuccess) { (void)hipGetLastError(); return aqg_fail(ctx, AQG_ERR_NOMEM, "group-by: no memory for the ranking bitmap"); }
-                ctx->rank_bm_words = nwords;
-                AQG_HIP(ctx, hipMemsetAsync(ctx->rank_bm, 0, (size_t)nwords * 4, ctx->stream));
+                if (hipMalloc(&ctx->rank_bm, (size_t)p.nwords * 4) != hipSuccess) { (void)hipGetLastError(); return aqg_fail(ctx, AQG_ERR_NOMEM, "group-by: no memory for the ranking bitmap"); }
+                ctx->rank_bm_words = p.nwords;
+                AQG_HIP(ctx, hipMemsetAsync(ctx->rank_bm, 0, (size_t)p.nwords * 4, ctx->stream));
             }
-            bitmap = ctx->rank_bm;
-            AQG_TRY(aqg_ws_get(ctx, ntiles + 1, &tile_mark));
-        } else AQG_TRY(aqg_ws_get(ctx, nwords, &bitmap));
-        AQG_TRY(aqg_ws_get(ctx, nwords, &word_prefix));
-        AQG_TRY(aqg_ws_get(ctx, ntiles + 1, &tile_total));
+            b.bitmap = ctx->rank_bm;
+            AQG_TRY(aqg_ws_get(ctx, p.ntiles + 1, &b.tile_mark));
+        } else AQG_TRY(aqg_ws_get(ctx, p.nwords, &b.bitmap));
+        AQG_TRY(aqg_ws_get(ctx, p.nwords, &b.word_prefix));
+        AQG_TRY(aqg_ws_get(ctx, p.ntiles + 1, &b.tile_total));
     }
-    if (!use_part && !use_wpart) hipLaunchKernelGGL(gt_init_kernel, dim3(aqg_grid(ctx, slots, 256, 1, 8)), dim3(256), 0, ctx->stream, gt, as);
+    if (!p.use_part && !p.use_wpart) hipLaunchKernelGGL(gt_init_kernel, dim3(aqg_grid(ctx, slots, 256, 1, 8)), dim3(256), 0, ctx->stream, gt, as);
     else AQG_HIP(ctx, hipMemsetAsync(gt.flags, 0, 64 * 4, ctx->stream));
-    if (bitmap && !sparse_rank) AQG_HIP(ctx, hipMemsetAsync(bitmap, 0, (size_t)nwords * 4, ctx->stream));
-    if (tile_mark) AQG_HIP(ctx, hipMemsetAsync(tile_mark, 0, ((size_t)ntiles + 1) * 4, ctx->stream));
+    if (b.bitmap && !p.sparse_rank) AQG_HIP(ctx, hipMemsetAsync(b.bitmap, 0, (size_t)p.nwords * 4, ctx->stream));
+    if (b.tile_mark) AQG_HIP(ctx, hipMemsetAsync(b.tile_mark, 0, ((size_t)p.ntiles + 1) * 4, ctx->stream));
+    return AQG_OK;
+}
 
-    // fast path eligibility: LDS mode, 16-byte aligned columns, one or two 4-byte integer keys or one 8-byte key, up to four accumulators
-    // of any kind over integer / floating value columns (also the first pass of aqg_groupby_build: no accumulators, only the distinct keys)
-    auto key32 = [&](int j) { return (ks.dt[j] == AQG_INT32 || ks.dt[j] == AQG_UINT32) && ((uintptr_t)ks.col[j] & 15) == 0; };
-    // two 4-byte key columns, or one 8-byte key column whose bits are the packed key
-    static const bool fast64_off = getenv("AQG_DISABLE_FAST64") != nullptr;                  // A/B measurements only (read once per process)
-    const bool fast_key8 = ks.nkeys == 1 && !ks.wide && (ks.dt[0] == AQG_INT64 || ks.dt[0] == AQG_UINT64) && ((uintptr_t)ks.col[0] & 15) == 0 && !fast64_off;
-    const bool fast_k64 = (ks.nkeys == 2 && !ks.wide && ks.total_bytes == 8 && key32(0) && key32(1)) || fast_key8;
-    bool fast = use_lds && !plan.sj && !big_lds && ((k32 && key32(0)) || fast_k64) && n >= 8 && (as.nacc >= 1 || plan.need_count || for_build) && as.nacc <= 4;
-    FastVals fv;
-    memset(&fv, 0, sizeof fv);
-    // value columns: 4 bytes wide, or 4 and 8 bytes wide (an int64 sum takes two accumulators)
-    auto wide_dt = [](int dt) { return dt == AQG_INT64 || dt == AQG_UINT64 || dt == AQG_DOUBLE; };
-    auto narrow_dt = [](int dt) { return dt == AQG_INT32 || dt == AQG_UINT32 || dt == AQG_FLOAT; };
-    auto tiny_dt = [](int dt) { return dt == AQG_INT8 || dt == AQG_UINT8 || dt == AQG_BOOL || dt == AQG_INT16 || dt == AQG_UINT16; };
-    bool fast_v8 = false;                       // some value column is 1, 2 or 8 bytes wide: the VW = 8 instantiation (it takes 4-byte ones, too)
-    for (int a = 0; a < as.nacc; ++a) fast_v8 = fast_v8 || wide_dt(as.dt[a]) || tiny_dt(as.dt[a]);
-    fast_v8 = fast_v8 && !fast64_off;
-    for (int a = 0; a < as.nacc && fast; ++a) {
-        const int dt = as.dt[a];
-        if ((uintptr_t)as.col[a] & 15) fast = false;
-        if (fast_v8) { if (!wide_dt(dt) && !narrow_dt(dt) && !tiny_dt(dt)) fast = false; }
-        else if (as.part[a] || !narrow_dt(dt)) fast = false;
-        fv.col[a] = as.col[a];
-        fv.vkind[a] = dt == AQG_INT32 ? 0 : dt == AQG_UINT32 ? 1 : dt == AQG_FLOAT ? 2 : dt == AQG_INT64 ? 3 : dt == AQG_UINT64 ? 4 : dt == AQG_DOUBLE ? 5 :
-                      dt == AQG_INT8 ? 6 : (dt == AQG_UINT8 || dt == AQG_BOOL) ? 7 : dt == AQG_INT16 ? 8 : 9;
-        fv.kind[a] = as.kind[a];
-        fv.square[a] = as.square[a];
-        fv.part[a] = as.part[a];
+int pass_starjoin(aqg_ctx* ctx, const AggPlan& p, const GTable& gt) {
+    const size_t lds = (size_t)(p.lcap + 1) * 24 + (size_t)p.plan.sj->dcap * 8 + 64;
+    const unsigned bpc = lds <= 20 * 1024 ? 8 : lds <= 40 * 1024 ? 4 : lds <= 80 * 1024 ? 2 : 1;
+    AQG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&starjoin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    aqg_kernel_timer_begin(ctx);
+    hipLaunchKernelGGL(starjoin_kernel, dim3(aqg_grid(ctx, p.n / 8 + 1, 256, 2, bpc)), dim3(256), lds, ctx->stream, static_cast<const uint32_t*>(p.ks.col[0]), *p.plan.sj, gt, p.n, p.lcap);
+    aqg_kernel_timer_end(ctx);
+    return aqg_check_launch(ctx, "starjoin_kernel");
+}
+
+int pass_fast(aqg_ctx* ctx, const AggPlan& p, const GTable& gt) {
+    const size_t lds = (size_t)(p.lcap + 1) * ((p.fast_k64 ? 8 : 4) + 8 * (size_t)p.plan.as.nacc + (p.plan.need_count ? 4 : 0)) + 64;
+    // the table is sized by the hint, not by the groups that show up: a large one leaves room for few workgroups per CU, and with 256
+    // threads each the LDS round trips of two accumulators per row are no longer hidden (var(v1), 100 groups, hint 1024: two
+    // workgroups = 8 wavefronts per CU ran at 43 % of the HBM roofline).  So the workgroup grows with the table: 32 wavefronts per CU.
+    const unsigned block = lds <= 20 * 1024 ? 256 : lds <= 40 * 1024 ? 512 : 1024;
+    const unsigned bpc = lds <= 20 * 1024 ? 8 : lds <= 40 * 1024 ? 4 : lds <= 78 * 1024 ? 2 : 1;
+    const unsigned grid = aqg_grid(ctx, p.n / 8 + 1, block, 2, bpc);
+    // (more workgroups than fit the chip cost more in table merges than they gain: 8192 -> +3 %, 32768 -> +30 % on Q1)
+    const uint32_t* khi = p.fast_k64 && !p.fast_key8 ? static_cast<const uint32_t*>(p.ks.col[1]) : nullptr;
+    return aqg_fast_aggregate(ctx, static_cast<const uint32_t*>(p.ks.col[0]), khi, p.fast_k64, p.fast_v8, p.plan.as.nacc, p.plan.need_count != 0, p.fv, gt, p.n, p.lcap, lds, grid, block);
+}
+
+// the partition plans; the packing and range-partition bits of h->plan_bits are learned here
+int pass_partitions(aqg_ctx* ctx, const AggPlan& p, aqg_groupby* h, AggBufs& b) {
+    const KeySpec& ks = p.ks;
+    const AccSpec& as = p.plan.as;
+    const size_t mark = ctx->ws_off;
+    PartRows* rows = p.for_build && !p.lookup_build ? &b.prows : nullptr;       // the build's id pass reads the partitioned rows
+    int pack = h->no_pack ? 0 : 1;
+    switch (p.pass) {
+    case RowPass::PART_WIDE:
+        AQG_TRY(aqg_partitionw_aggregate(ctx, ks, as, p.n, p.plan.need_count, b.gt, p.gcap, h->wide_seed, p.hint, &pack, &h->wide_rows, p.rows_possible));
+        if (pack) h->plan_bits |= AQG_PLAN_PACKED_KEYS;
+        break;
+    case RowPass::PART_ONE:
+        AQG_TRY(aqg_partition1_aggregate(ctx, ks, as, p.n, p.p1_bins, p.plan.need_count, b.gt, p.gcap, rows, p.part_layout, &pack));
+        if (pack & 2) h->plan_bits |= AQG_PLAN_RANGE_PARTITIONS;
+        if (pack & 1) h->plan_bits |= AQG_PLAN_PACKED_VALUES;
+        break;
+    case RowPass::PART_TWO:
+        AQG_TRY(aqg_partition2_aggregate(ctx, ks, as, p.n, p.p2_parts, p.plan.need_count, b.gt, p.gcap, rows, &pack, p.part_layout));
+        if (pack & 1) h->plan_bits |= AQG_PLAN_PACKED_VALUES;
+        if (pack & 2) h->plan_bits |= AQG_PLAN_RANGE_PARTITIONS;
+        break;
+    default: AQG_TRY(aqg_partition_aggregate(ctx, ks, as, p.n, p.pbits, p.part_lcap, p.plan.need_count, b.gt, p.gcap));
     }
-    // ---- pass over the rows ---------------------------------------------------------------------
-    if (n && plan.sj) {
-        const size_t lds = (size_t)(lcap + 1) * 24 + (size_t)plan.sj->dcap * 8 + 64;
-        unsigned bpc = lds <= 20 * 1024 ? 8 : lds <= 40 * 1024 ? 4 : lds <= 80 * 1024 ? 2 : 1;
-        AQG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&starjoin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        aqg_kernel_timer_begin(ctx);
-        hipLaunchKernelGGL(starjoin_kernel, dim3(aqg_grid(ctx, n / 8 + 1, 256, 2, bpc)), dim3(256), lds, ctx->stream, static_cast<const uint32_t*>(ks.col[0]), *plan.sj, gt, n, lcap);
-        aqg_kernel_timer_end(ctx);
-        AQG_TRY(aqg_check_launch(ctx, "starjoin_kernel"));
-    } else if (n && fast) {
-        const size_t lds = (size_t)(lcap + 1) * ((fast_k64 ? 8 : 4) + 8 * (size_t)as.nacc + (plan.need_count ? 4 : 0)) + 64;
-        // the table is sized by the hint, not by the groups that show up: a large one leaves room for few workgroups per CU, and with 256
-        // threads each the LDS round trips of two accumulators per row are no longer hidden (var(v1), 100 groups, hint 1024: two
-        // workgroups = 8 wavefronts per CU ran at 43 % of the HBM roofline).  So the workgroup grows with the table: 32 wavefronts per CU.
-        static const unsigned block_env = getenv("AQG_FAST_BLOCK") ? (unsigned)atoi(getenv("AQG_FAST_BLOCK")) : 0;
-        const unsigned block = block_env ? block_env : lds <= 20 * 1024 ? 256 : lds <= 40 * 1024 ? 512 : 1024;
-        unsigned bpc = lds <= 20 * 1024 ? 8 : lds <= 40 * 1024 ? 4 : lds <= 78 * 1024 ? 2 : 1;
-        unsigned grid = aqg_grid(ctx, n / 8 + 1, block, 2, bpc);
-        // (more workgroups than fit the chip cost more in table merges than they gain: 8192 -> +3 %, 32768 -> +30 % on Q1)
-        const uint32_t* khi = fast_k64 && !fast_key8 ? static_cast<const uint32_t*>(ks.col[1]) : nullptr;
-        h->plan_bits = AQG_PLAN_FAST_LDS;
-        const int rc = aqg_fast_aggregate(ctx, static_cast<const uint32_t*>(ks.col[0]), khi, fast_k64, fast_v8, as.nacc, plan.need_count != 0, fv, gt, n, lcap, lds, grid, block);
-        AQG_TRY(rc);
-    } else if (n && dense) {
-        h->plan_bits = AQG_PLAN_DENSE;
-        AQG_TRY(aqg_dense_aggregate(ctx, ks, dspec, as, n, plan.need_count, gt));
-    } else if (n && (use_wpart || use_part)) {
-        const size_t mark = ctx->ws_off;
-        memset(&prows, 0, sizeof prows);
-        h->plan_bits = (use_wpart ? AQG_PLAN_PART_WIDE : p1_bins ? AQG_PLAN_PART_ONE : p2_parts ? AQG_PLAN_PART_TWO : AQG_PLAN_PART_ROUND1) | (sorted_tail ? AQG_PLAN_SORTED_TAIL : 0u);
-        if (use_wpart) {
-            int pack = h->no_pack ? 0 : 1;
-            AQG_TRY(aqg_partitionw_aggregate(ctx, ks, as, n, plan.need_count, gt, gcap, h->wide_seed, hint, &pack, &h->wide_rows, rows_possible));
-            if (pack) h->plan_bits |= AQG_PLAN_PACKED_KEYS;
-        }
-        else if (p1_bins) {
-            int ranged = h->no_pack ? 0 : 1;
-            AQG_TRY(aqg_partition1_aggregate(ctx, ks, as, n, p1_bins, plan.need_count, gt, gcap, for_build && !lookup_build ? &prows : nullptr, part_layout, &ranged));
-            if (ranged & 2) h->plan_bits |= AQG_PLAN_RANGE_PARTITIONS;
-            if (ranged & 1) h->plan_bits |= AQG_PLAN_PACKED_VALUES;
-        }
-        else if (p2_parts) {
-            int pack = h->no_pack ? 0 : 1;
-            AQG_TRY(aqg_partition2_aggregate(ctx, ks, as, n, p2_parts, plan.need_count, gt, gcap, for_build && !lookup_build ? &prows : nullptr, &pack, part_layout));
-            if (pack & 1) h->plan_bits |= AQG_PLAN_PACKED_VALUES;
-            if (pack & 2) h->plan_bits |= AQG_PLAN_RANGE_PARTITIONS;
-        }
-        else AQG_TRY(aqg_partition_aggregate(ctx, ks, as, n, pbits, part_lcap, plan.need_count, gt, gcap));
-        if (sorted_tail) ctx->ws_off = mark;       // stream order: whatever is allocated there next is written after these kernels
-        else hipLaunchKernelGGL(occ_iota_kernel, dim3(aqg_grid(ctx, slots, 256, 1, 8)), dim3(256), 0, ctx->stream, occ, (uint32_t)slots);
-    } else if (n) {
-        uint32_t lrep = 1;
-        if (use_lds) {   // replicate small tables: conflicts fall, LDS stays under ~32 KB per workgroup
-            size_t per = (size_t)(lcap + 1) * (8 + 8 * (size_t)as.nacc + (k32 ? 0 : 4) + (plan.need_count ? 4 : 0));
-            uint32_t want = 1;   // measured on MI355X (h2o Q1, 100 groups): 1 replica 1.98 ms, 4 replicas 2.12 ms per 1e9 rows
-            while (lrep < want && per * lrep * 2 <= 64 * 1024) lrep *= 2;
-        }
-        size_t lds = use_lds ? (size_t)lrep * (lcap + 1) * (8 + 8 * (size_t)as.nacc + (k32 ? 0 : 4) + (plan.need_count ? 4 : 0)) + 4 * 64 : 0;
-        unsigned bpc = !use_lds ? 8 : lds <= 20 * 1024 ? 8 : lds <= 40 * 1024 ? 4 : lds <= 80 * 1024 ? 2 : 1;
-        h->plan_bits = big_lds ? AQG_PLAN_BIG_LDS : use_lds ? AQG_PLAN_SMALL_LDS : AQG_PLAN_HBM_TABLE;
-        const unsigned block = big_lds ? (as.nacc <= 2 ? 1024 : 512) : 256;
-        unsigned grid = big_lds ? (unsigned)ctx->num_cu : aqg_grid(ctx, n / 4 + 1, 256, 2, bpc);
-        auto launch = [&](auto kern) -> int {
-            if (lds) AQG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, ctx->stream, ks, as, gt, n, lcap, plan.need_count, lrep, npass);
-            return AQG_OK;
-        };
-        auto by_nacc = [&](auto lds_tag, auto k32_tag, auto block_tag) -> int {
-            constexpr bool L = decltype(lds_tag)::value, K = decltype(k32_tag)::value;
-            constexpr int B = decltype(block_tag)::value;
-            // big tables: 1024 threads per workgroup up to 2 accumulators (<= 128 VGPRs without spills), 512 beyond
-#define AQG_AGG_CASE(N) case N: if constexpr ((B == 1024 && N > 2) || (B == 512 && N <= 2)) return AQG_ERR_ARG; else return launch(&agg_kernel<L, K, N, B>);
-            switch (as.nacc) {
-            AQG_AGG_CASE(0) AQG_AGG_CASE(1) AQG_AGG_CASE(2) AQG_AGG_CASE(3) AQG_AGG_CASE(4) AQG_AGG_CASE(5) AQG_AGG_CASE(6) AQG_AGG_CASE(7)
-            default: if constexpr (B == 1024) return AQG_ERR_ARG; else return launch(&agg_kernel<L, K, 8, B>);
-            }
-#undef AQG_AGG_CASE
-        };
-        using B256 = std::integral_constant<int, 256>;
-        using B512 = std::integral_constant<int, 512>;
-        using B1024 = std::integral_constant<int, 1024>;
-        aqg_kernel_timer_begin(ctx);
-        if (big_lds && block == 1024) { if (k32) AQG_TRY(by_nacc(std::true_type{}, std::true_type{}, B1024{})); else AQG_TRY(by_nacc(std::true_type{}, std::false_type{}, B1024{})); }
-        else if (big_lds) { if (k32) AQG_TRY(by_nacc(std::true_type{}, std::true_type{}, B512{})); else AQG_TRY(by_nacc(std::true_type{}, std::false_type{}, B512{})); }
-        else if (use_lds) { if (k32) AQG_TRY(by_nacc(std::true_type{}, std::true_type{}, B256{})); else AQG_TRY(by_nacc(std::true_type{}, std::false_type{}, B256{})); }
-        else { if (k32) AQG_TRY(by_nacc(std::false_type{}, std::true_type{}, B256{})); else AQG_TRY(by_nacc(std::false_type{}, std::false_type{}, B256{})); }
-        aqg_kernel_timer_end(ctx);
-        AQG_TRY(aqg_check_launch(ctx, "agg_kernel"));
-    }
-    // ---- dense ids ---------------------------------------------------------------------------------
-    unsigned cgrid = aqg_grid(ctx, slots, 256, 1, 8);
-    if (!(n && (use_part || use_wpart))) hipLaunchKernelGGL(collect_kernel, dim3(cgrid), dim3(256), 0, ctx->stream, gt, occ);
-    uint32_t fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};        // [0] overflow, [1] occupied slots, [3] a row outside the sampled key ranges, [4], [5] diagnostics, [6] a value outside its packed field
-    uint32_t G = 0;
-    auto judge_flags = [&]() -> int {
-        if (dense && fl[3]) { h->dense_exact = true; h->range_valid = false; return AQG_ERR_RANGE_MISS; }
-        if (use_wpart && fl[6]) { h->no_pack = true; return AQG_ERR_RANGE_MISS; }      // a key outside the sampled range of its packed field: once more, unpacked
-        if (use_wpart && fl[0]) {
-            // a partition larger than LDS holds (fl[5] rows).  A little over: chance (a million partitions sized at mean + 6 sigma) --
-            // ONE more try with another seed of the partition hash; far over, or over again: a tuple that dominates the input, which no
-            // seed spreads -- the HBM table, same hint
-            static const bool debug_flags = getenv("AQG_DEBUG_FLAGS") != nullptr;
-            if (debug_flags) fprintf(stderr, "aqg: wide partition plan gave up: flags %u %u %u %u, partition %u holds %u rows (n %u, hint %u, seed %u)\n", fl[0], fl[1], fl[2], fl[3], fl[4], fl[5], n, hint, h->wide_seed);
-            const uint32_t rcap = h->wide_rows ? h->wide_rows : aqg_partitionw_rows(ks, as, n, hint);
-            if (!fl[5]) return AQG_ERR_OVERFLOW;     // no partition was too large: the record table (out_cap) was -- more groups than hinted, the caller grows the hint
-            if (h->wide_seed == 0 && fl[5] <= rcap + rcap / 2) h->wide_seed = 0x5BD1E995u; else h->no_wide_part = true;
-            return AQG_ERR_RANGE_MISS;
-        }
-        if ((use_part || use_wpart) && fl[6]) { h->no_pack = true; return AQG_ERR_RANGE_MISS; }     // a value outside the sampled range of its packed field: once more, unpacked
-        if (fl[0]) return AQG_ERR_OVERFLOW;
-        G = fl[1];
-        if (small_rank && G > 4096) return AQG_ERR_OVERFLOW;
-        if (use_lds && G > lds_group_cap && G > hint) return AQG_ERR_OVERFLOW;   // correct but slow (overflow rows took the HBM path): re-plan
+    if (p.sorted_tail) ctx->ws_off = mark;       // stream order: whatever is allocated there next is written after these kernels
+    else hipLaunchKernelGGL(occ_iota_kernel, dim3(aqg_grid(ctx, b.slots, 256, 1, 8)), dim3(256), 0, ctx->stream, b.occ, (uint32_t)b.slots);
+    return AQG_OK;
+}
+
+// the hashed table: LDS (one or MAX_PASSES hash classes) or HBM
+int pass_hashed(aqg_ctx* ctx, const AggPlan& p, const GTable& gt) {
+    const AccSpec& as = p.plan.as;
+    // (one table per workgroup: replicas were measured slower on MI355X, h2o Q1, 100 groups: 1 replica 1.98 ms, 4 replicas 2.12 ms per 1e9 rows)
+    const size_t lds = p.use_lds ? (size_t)(p.lcap + 1) * p.lds_slot_bytes + 4 * 64 : 0;
+    const unsigned bpc = !p.use_lds ? 8 : lds <= 20 * 1024 ? 8 : lds <= 40 * 1024 ? 4 : lds <= 80 * 1024 ? 2 : 1;
+    const unsigned block = p.big_lds ? (as.nacc <= 2 ? 1024 : 512) : 256;
+    const unsigned grid = p.big_lds ? (unsigned)ctx->num_cu : aqg_grid(ctx, p.n / 4 + 1, 256, 2, bpc);
+    auto launch = [&](auto kern) -> int {
+        if (lds) AQG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, ctx->stream, p.ks, as, gt, p.n, p.lcap, p.plan.need_count, 1u, p.npass);
         return AQG_OK;
     };
-    auto read_flags = [&]() -> int {
-        AQG_HIP(ctx, hipMemcpyAsync(fl, gt.flags, 32, hipMemcpyDeviceToHost, ctx->stream));
-        AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return judge_flags();
+    auto by_nacc = [&](auto lds_tag, auto k32_tag, auto block_tag) -> int {
+        constexpr bool L = decltype(lds_tag)::value, K = decltype(k32_tag)::value;
+        constexpr int B = decltype(block_tag)::value;
+        // big tables: 1024 threads per workgroup up to 2 accumulators (<= 128 VGPRs without spills), 512 beyond
+#define AQG_AGG_CASE(N) case N: if constexpr ((B == 1024 && N > 2) || (B == 512 && N <= 2)) return AQG_ERR_ARG; else return launch(&agg_kernel<L, K, N, B>);
+        switch (as.nacc) {
+        AQG_AGG_CASE(0) AQG_AGG_CASE(1) AQG_AGG_CASE(2) AQG_AGG_CASE(3) AQG_AGG_CASE(4) AQG_AGG_CASE(5) AQG_AGG_CASE(6) AQG_AGG_CASE(7)
+        default: if constexpr (B == 1024) return AQG_ERR_ARG; else return launch(&agg_kernel<L, K, 8, B>);
+        }
+#undef AQG_AGG_CASE
     };
-    // The fast kernel or the fused star join with a small table (h2o Q1 / Q4, config 4): every kernel of the tail reads the group count from the device flags and
-    // the outputs are sized by the table, so nothing on the host stands between collect and emit (a round trip there cost 26 us
-    // of a 1.45 ms step).  The flag words -- final once collect has run -- are copied to pinned memory right here, behind
-    // collect and in FRONT of the tail, and the host waits for that copy only: the call returns with first rows / rank / emit
-    // still queued (stream-ordered, like every device result of this library), so the host's way to the next call overlaps them.
-    // An overflow is noticed with the tail already queued on it: those kernels are bounded by the table and by `gmax`, their
-    // results are discarded and the call re-plans as before.
-    const bool defer = n && (fast || plan.sj) && small_rank && !dense && !use_part && !use_wpart;
-    const uint32_t gupper = (uint32_t)(slots + 1 < 4096 ? slots + 1 : 4096);
-    uint32_t* pinned_flags = nullptr;
-    if (defer) {
-        AQG_TRY(aqg_host_stage(ctx, 16, reinterpret_cast<void**>(&pinned_flags)));
-        AQG_HIP(ctx, hipMemcpyAsync(pinned_flags, gt.flags, 16, hipMemcpyDeviceToHost, ctx->stream));
-        AQG_HIP(ctx, hipEventRecord(ctx->ev_flags, ctx->stream));
+    auto by_k32 = [&](auto lds_tag, auto block_tag) -> int { return p.k32 ? by_nacc(lds_tag, std::true_type{}, block_tag) : by_nacc(lds_tag, std::false_type{}, block_tag); };
+    aqg_kernel_timer_begin(ctx);
+    if (p.big_lds && block == 1024) AQG_TRY(by_k32(std::true_type{}, std::integral_constant<int, 1024>{}));
+    else if (p.big_lds) AQG_TRY(by_k32(std::true_type{}, std::integral_constant<int, 512>{}));
+    else if (p.use_lds) AQG_TRY(by_k32(std::true_type{}, std::integral_constant<int, 256>{}));
+    else AQG_TRY(by_k32(std::false_type{}, std::integral_constant<int, 256>{}));
+    aqg_kernel_timer_end(ctx);
+    return aqg_check_launch(ctx, "agg_kernel");
+}
+
+// the plan a row pass stands for in h->plan_bits (the star join has no bit of its own)
+uint32_t row_pass_bits(const AggPlan& p) {
+    constexpr uint32_t bits[] = {0, AQG_PLAN_FAST_LDS, AQG_PLAN_DENSE, AQG_PLAN_PART_WIDE, AQG_PLAN_PART_ONE, AQG_PLAN_PART_TWO, AQG_PLAN_PART_ROUND1};   // (RowPass order)
+    if (p.pass == RowPass::HASHED) return p.big_lds ? AQG_PLAN_BIG_LDS : p.use_lds ? AQG_PLAN_SMALL_LDS : AQG_PLAN_HBM_TABLE;
+    return bits[(int)p.pass] | (p.sorted_tail ? AQG_PLAN_SORTED_TAIL : 0u);      // (only partition plans order their records)
+}
+
+// the pass over the rows, then collect: the ids of the occupied slots (the partition plans wrote them already)
+int row_pass(aqg_ctx* ctx, const AggPlan& p, aqg_groupby* h, AggBufs& b) {
+    if (p.n) {
+        if (p.pass != RowPass::STARJOIN) h->plan_bits = row_pass_bits(p);
+        switch (p.pass) {
+        case RowPass::STARJOIN: AQG_TRY(pass_starjoin(ctx, p, b.gt)); break;
+        case RowPass::FAST_LDS: AQG_TRY(pass_fast(ctx, p, b.gt)); break;
+        case RowPass::DENSE: AQG_TRY(aqg_dense_aggregate(ctx, p.ks, p.dspec, p.plan.as, p.n, p.plan.need_count, b.gt)); break;
+        case RowPass::HASHED: AQG_TRY(pass_hashed(ctx, p, b.gt)); break;
+        default: AQG_TRY(pass_partitions(ctx, p, h, b));
+        }
     }
-    if (!defer) AQG_TRY(read_flags());
-    if ((defer || G) && n && fast) {
+    if (!(p.n && (p.use_part || p.use_wpart))) hipLaunchKernelGGL(collect_kernel, dim3(aqg_grid(ctx, b.slots, 256, 1, 8)), dim3(256), 0, ctx->stream, b.gt, b.occ);
+    return AQG_OK;
+}
+
+// The flag words ([0] overflow, [1] occupied slots, [3] a row outside the sampled key ranges, [4], [5] diagnostics, [6] a value outside
+// its packed field): a retry -- remembered in the handle -- an overflow, or the group count *G
+int judge_flags(const AggPlan& p, const uint32_t* fl, aqg_groupby* h, uint32_t* G) {
+    if (p.dense && fl[3]) { h->dense_exact = true; h->range_valid = false; return AQG_ERR_RANGE_MISS; }
+    if (p.use_wpart && fl[6]) { h->no_pack = true; return AQG_ERR_RANGE_MISS; }      // a key outside the sampled range of its packed field: once more, unpacked
+    if (p.use_wpart && fl[0]) {
+        // a partition larger than LDS holds (fl[5] rows).  A little over: chance (a million partitions sized at mean + 6 sigma) --
+        // ONE more try with another seed of the partition hash; far over, or over again: a tuple that dominates the input, which no
+        // seed spreads -- the HBM table, same hint
+        if (aqg_switches().debug_flags) fprintf(stderr, "aqg: wide partition plan gave up: flags %u %u %u %u, partition %u holds %u rows (n %u, hint %u, seed %u)\n", fl[0], fl[1], fl[2], fl[3], fl[4], fl[5], p.n, p.hint, h->wide_seed);
+        const uint32_t rcap = h->wide_rows ? h->wide_rows : aqg_partitionw_rows(p.ks, p.plan.as, p.n, p.hint);
+        if (!fl[5]) return AQG_ERR_OVERFLOW;     // no partition was too large: the record table (out_cap) was -- more groups than hinted, the caller grows the hint
+        if (h->wide_seed == 0 && fl[5] <= rcap + rcap / 2) h->wide_seed = 0x5BD1E995u; else h->no_wide_part = true;
+        return AQG_ERR_RANGE_MISS;
+    }
+    if ((p.use_part || p.use_wpart) && fl[6]) { h->no_pack = true; return AQG_ERR_RANGE_MISS; }     // a value outside the sampled range of its packed field: once more, unpacked
+    if (fl[0]) return AQG_ERR_OVERFLOW;
+    *G = fl[1];
+    if (p.small_rank && *G > 4096) return AQG_ERR_OVERFLOW;
+    if (p.use_lds && *G > p.lds_group_cap && *G > p.hint) return AQG_ERR_OVERFLOW;   // correct but slow (overflow rows took the HBM path): re-plan
+    return AQG_OK;
+}
+
+// The fast kernel or the fused star join with a small table (h2o Q1 / Q4, config 4): every kernel of the tail reads the group count from the device flags and
+// the outputs are sized by the table, so nothing on the host stands between collect and emit (a round trip there cost 26 us
+// of a 1.45 ms step).  The flag words -- final once collect has run -- are copied to pinned memory right here, behind
+// collect and in FRONT of the tail, and the host waits for that copy only: the call returns with first rows / rank / emit
+// still queued (stream-ordered, like every device result of this library), so the host's way to the next call overlaps them.
+// An overflow is noticed with the tail already queued on it: those kernels are bounded by the table and by `gmax`, their
+// results are discarded and the call re-plans as before.
+int read_flags(aqg_ctx* ctx, const AggPlan& p, aqg_groupby* h, AggBufs& b, uint32_t* G) {
+    if (p.defer) {
+        AQG_TRY(aqg_host_stage(ctx, 16, reinterpret_cast<void**>(&b.pinned_flags)));
+        AQG_HIP(ctx, hipMemcpyAsync(b.pinned_flags, b.gt.flags, 16, hipMemcpyDeviceToHost, ctx->stream));
+        AQG_HIP(ctx, hipEventRecord(ctx->ev_flags, ctx->stream));
+        return AQG_OK;
+    }
+    uint32_t fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    AQG_HIP(ctx, hipMemcpyAsync(fl, b.gt.flags, 32, hipMemcpyDeviceToHost, ctx->stream));
+    AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return judge_flags(p, fl, h, G);
+}
+
+// first rows (fast path), then the group order: none for a row map, the ordering tail, or ranks through a small table / the bitmap
+int rank_groups(aqg_ctx* ctx, const AggPlan& p, const AggBufs& b, uint32_t G, bool row_emit, SortedParts* sparts) {
+    const uint32_t n = p.n;
+    const GTable& gt = b.gt;
+    if ((p.defer || G) && n && p.fast) {
         // two launches: 32 workgroups over the first 32768 rows (where every group of an h2o-like column already shows up), then
         // the whole chip over the rest, whose workgroups leave at once when nothing is missing.  One launch of 256 workgroups
         // starts with 65536 lanes pushing atomicMin at ~100 addresses: 28-31 us on h2o Q1.
-        const uint32_t* k0 = static_cast<const uint32_t*>(ks.col[0]);
-        const uint32_t* k1 = fast_k64 && !fast_key8 ? static_cast<const uint32_t*>(ks.col[1]) : (const uint32_t*)nullptr;
+        const uint32_t* k0 = static_cast<const uint32_t*>(p.ks.col[0]);
+        const uint32_t* k1 = p.fast_k64 && !p.fast_key8 ? static_cast<const uint32_t*>(p.ks.col[1]) : (const uint32_t*)nullptr;
         const uint32_t head_tiles = 32, head_rows = head_tiles * 1024;
-        hipLaunchKernelGGL(first_rows_kernel, dim3(head_tiles), dim3(256), 0, ctx->stream, k0, k1, fast_key8 ? 1 : 0, 0u, n < head_rows ? n : head_rows, gt, (const uint32_t*)occ);
+        hipLaunchKernelGGL(first_rows_kernel, dim3(head_tiles), dim3(256), 0, ctx->stream, k0, k1, p.fast_key8 ? 1 : 0, 0u, n < head_rows ? n : head_rows, gt, (const uint32_t*)b.occ);
         if (n > head_rows) {
             unsigned fgrid = aqg_grid(ctx, (n - head_rows) / 4 + 1, 256, 1, 1);
-            hipLaunchKernelGGL(first_rows_kernel, dim3(fgrid), dim3(256), 0, ctx->stream, k0, k1, fast_key8 ? 1 : 0, head_tiles, n, gt, (const uint32_t*)occ);
+            hipLaunchKernelGGL(first_rows_kernel, dim3(fgrid), dim3(256), 0, ctx->stream, k0, k1, p.fast_key8 ? 1 : 0, head_tiles, n, gt, (const uint32_t*)b.occ);
         }
         AQG_TRY(aqg_check_launch(ctx, "first_rows_kernel"));
     }
-    // every row its own group: the result is a map of the input (emit_rows_kernel) -- nothing to rank or order
-    const bool row_emit = rows_possible && !defer && G == n && (use_part || use_wpart);
-    SortedParts sparts;
-    if (row_emit) {
-        h->plan_bits |= AQG_PLAN_ROW_EMIT;
-    } else if (sorted_tail && G) {
-        AQG_TRY(aqg_sorted_tail(ctx, gt, G, n, as.nacc, ks.wide != 0, &sparts));
-    } else if (defer || G) {
-        if (small_rank) {
-            hipLaunchKernelGGL(rank_small_kernel, dim3(1), dim3(1024), 0, ctx->stream, gt, occ, gid_of_occ, slot_gid);
-        } else {
-            unsigned g1 = aqg_grid(ctx, G, 256, 1, 8);
-            hipLaunchKernelGGL(bitmap_set_kernel, dim3(g1), dim3(256), 0, ctx->stream, gt, occ, bitmap, tile_mark);
-            hipLaunchKernelGGL(bitmap_tile_kernel, dim3(ntiles), dim3(256), 0, ctx->stream, bitmap, nwords, word_prefix, tile_total, (const uint32_t*)tile_mark);
-            hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, tile_total, ntiles);
-            hipLaunchKernelGGL(rank_bitmap_kernel, dim3(g1), dim3(256), 0, ctx->stream, gt, occ, bitmap, word_prefix, tile_total, gid_of_occ, slot_gid);
-            if (sparse_rank) hipLaunchKernelGGL(bitmap_clear_kernel, dim3(g1), dim3(256), 0, ctx->stream, gt, occ, bitmap);      // the context's bitmap is all zero again
-        }
+    if (row_emit) return AQG_OK;
+    if (p.sorted_tail && G) return aqg_sorted_tail(ctx, gt, G, n, p.plan.as.nacc, p.ks.wide != 0, sparts);
+    if (!(p.defer || G)) return AQG_OK;
+    if (p.small_rank) {
+        hipLaunchKernelGGL(rank_small_kernel, dim3(1), dim3(1024), 0, ctx->stream, gt, b.occ, b.gid_of_occ, b.slot_gid);
+    } else {
+        unsigned g1 = aqg_grid(ctx, G, 256, 1, 8);
+        hipLaunchKernelGGL(bitmap_set_kernel, dim3(g1), dim3(256), 0, ctx->stream, gt, b.occ, b.bitmap, b.tile_mark);
+        hipLaunchKernelGGL(bitmap_tile_kernel, dim3(p.ntiles), dim3(256), 0, ctx->stream, b.bitmap, p.nwords, b.word_prefix, b.tile_total, (const uint32_t*)b.tile_mark);
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, b.tile_total, p.ntiles);
+        hipLaunchKernelGGL(rank_bitmap_kernel, dim3(g1), dim3(256), 0, ctx->stream, gt, b.occ, b.bitmap, b.word_prefix, b.tile_total, b.gid_of_occ, b.slot_gid);
+        if (p.sparse_rank) hipLaunchKernelGGL(bitmap_clear_kernel, dim3(g1), dim3(256), 0, ctx->stream, gt, b.occ, b.bitmap);      // the context's bitmap is all zero again
     }
-    // ---- outputs --------------------------------------------------------------------------------------
+    return AQG_OK;
+}
+
+// the handle's result columns (sized by the table's bound while the flags are deferred), then the emit pass that fills them
+int emit_outputs(aqg_ctx* ctx, const AggPlan& p, aqg_groupby* h, const AggBufs& b, uint32_t G, bool row_emit, const SortedParts& sparts) {
+    const KeySpec& ks = p.ks;
+    const AccSpec& as = p.plan.as;
+    const uint32_t n = p.n;
+    const uint32_t gupper = (uint32_t)(b.slots + 1 < 4096 ? b.slots + 1 : 4096);
     h->nkeys = ks.nkeys;
-    size_t gcapn = defer ? gupper : (G ? G : 1);
-    EmitSpec es;
-    memset(&es, 0, sizeof es);
-    es.nkeys = ks.nkeys;
-    es.wide = ks.wide;
+    size_t gcapn = p.defer ? gupper : (G ? G : 1);
+    EmitSpec es{};
+    es.nkeys = ks.nkeys; es.wide = ks.wide;
     for (int k = 0; k < ks.nkeys; ++k) {
         h->key_dt[k] = ks.dt[k];
         AQG_TRY(dev_realloc(ctx, &h->keys_out[k], &h->cap_keys[k], gcapn * 8));
@@ -1616,13 +1668,13 @@ int run_agg(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint32_t n,
     AQG_TRY(dev_realloc(ctx, (void**)&h->first_rows, &h->cap_first, gcapn * 4));
     AQG_TRY(dev_realloc(ctx, (void**)&h->counts, &h->cap_counts, gcapn * 4));
     es.first_out = h->first_rows;
-    h->has_counts = plan.need_count && (!for_build || (use_part && n));
+    h->has_counts = p.plan.need_count && (!p.for_build || (p.use_part && n));
     es.count_out = h->has_counts ? h->counts : nullptr;
-    es.nagg = plan.nagg;
-    h->nagg = plan.nagg;
-    for (int j = 0; j < plan.nagg; ++j) {
-        es.agg[j] = plan.agg[j];
-        h->res_dt[j] = aqg_reduce_out_dtype(plan.agg[j].op, plan.agg[j].dt);
+    es.nagg = p.plan.nagg;
+    h->nagg = p.plan.nagg;
+    for (int j = 0; j < p.plan.nagg; ++j) {
+        es.agg[j] = p.plan.agg[j];
+        h->res_dt[j] = aqg_reduce_out_dtype(p.plan.agg[j].op, p.plan.agg[j].dt);
         AQG_TRY(dev_realloc(ctx, &h->results[j], &h->cap_results[j], gcapn * 16));
         es.agg[j].out = h->results[j];
     }
@@ -1635,69 +1687,91 @@ int run_agg(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint32_t n,
             } else AQG_HIP(ctx, hipMemcpyAsync(h->keys_out[k], ks.col[k], bytes, hipMemcpyDeviceToDevice, ctx->stream));
         }
         hipLaunchKernelGGL(emit_rows_kernel, dim3(aqg_grid(ctx, n, 256, 1, 8)), dim3(256), 0, ctx->stream, as, es, n);
-        AQG_TRY(aqg_check_launch(ctx, "emit_rows_kernel"));
-    } else if (sorted_tail && G) {
+        return aqg_check_launch(ctx, "emit_rows_kernel");
+    }
+    if (p.sorted_tail && G) {
         AQG_TRY(aqg_allow_lds(ctx, reinterpret_cast<const void*>(&sorted_emit_kernel), sparts.lds));
         const unsigned per_cu = sparts.lds <= 80 * 1024 ? 2 : 1;
         const unsigned sg = sparts.nparts < 4u * per_cu * ctx->num_cu ? sparts.nparts : 4u * per_cu * ctx->num_cu;
-        static const unsigned se_env = getenv("AQG_SORTED_EMIT_BLOCK") ? (unsigned)atoi(getenv("AQG_SORTED_EMIT_BLOCK")) : 1024u;
-        const unsigned se_block = se_env >= 512 && se_env <= 1024 && se_env % 64 == 0 ? se_env : 1024u;      // (one lane per bitmap word of a 16384-row interval: 512 at least)
-        hipLaunchKernelGGL(sorted_emit_kernel, dim3(sg), dim3(se_block), sparts.lds, ctx->stream, sparts, G, n, as.nacc, (int)gt.has_count, (int)(ks.wide != 0), es, gt.flags);
+        hipLaunchKernelGGL(sorted_emit_kernel, dim3(sg), dim3(SORTED_EMIT_BLOCK), sparts.lds, ctx->stream, sparts, G, n, as.nacc, (int)b.gt.has_count, (int)(ks.wide != 0), es, b.gt.flags);
         AQG_TRY(aqg_check_launch(ctx, "sorted_emit_kernel"));
         // a partition that does not keep to the plan (more records or a longer row interval than LDS was sized for) is skipped by the kernel
         // and reported in flag word 7: the output would miss its rows, so the call waits for the word (calls of this size run for tens of
         // milliseconds) and, should it ever be set, runs once more through the bitmap tail
         uint32_t bad = 0;
-        AQG_HIP(ctx, hipMemcpyAsync(&bad, gt.flags + 7, 4, hipMemcpyDeviceToHost, ctx->stream));
+        AQG_HIP(ctx, hipMemcpyAsync(&bad, b.gt.flags + 7, 4, hipMemcpyDeviceToHost, ctx->stream));
         AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (bad) { h->no_sorted_tail = true; return AQG_ERR_RANGE_MISS; }
-    } else if (defer || G) {
-        unsigned eg = aqg_grid(ctx, defer ? gupper : G, 256, 1, 8);
-        uint32_t* order = nullptr;
-        if (ordered_emit && G >= (1u << 20)) {
-            AQG_TRY(aqg_ws_get(ctx, slots, &order));
-            hipLaunchKernelGGL(emit_order_kernel, dim3(eg), dim3(256), 0, ctx->stream, (const uint32_t*)gid_of_occ, G, order);
-        }
-        hipLaunchKernelGGL(emit_kernel, dim3(eg), dim3(256), 0, ctx->stream, gt, (const uint32_t*)occ, (const uint32_t*)gid_of_occ, es, (const uint32_t*)order, defer ? 4096u : 0u, (int)(n && (use_part || use_wpart)));
-        AQG_TRY(aqg_check_launch(ctx, "emit_kernel"));
+        return AQG_OK;
     }
-    if (defer) {
-        AQG_HIP(ctx, hipEventSynchronize(ctx->ev_flags));
-        memcpy(fl, pinned_flags, 16);
-        AQG_TRY(judge_flags());
-        ctx->tail_in_flight = true;
+    if (!(p.defer || G)) return AQG_OK;
+    unsigned eg = aqg_grid(ctx, p.defer ? gupper : G, 256, 1, 8);
+    uint32_t* order = nullptr;
+    if (p.ordered_emit && G >= (1u << 20)) {
+        AQG_TRY(aqg_ws_get(ctx, b.slots, &order));
+        hipLaunchKernelGGL(emit_order_kernel, dim3(eg), dim3(256), 0, ctx->stream, (const uint32_t*)b.gid_of_occ, G, order);
     }
+    hipLaunchKernelGGL(emit_kernel, dim3(eg), dim3(256), 0, ctx->stream, b.gt, (const uint32_t*)b.occ, (const uint32_t*)b.gid_of_occ, es, (const uint32_t*)order, p.defer ? 4096u : 0u, (int)(n && (p.use_part || p.use_wpart)));
+    return aqg_check_launch(ctx, "emit_kernel");
+}
+
+// aqg_groupby_build over a partition plan: the group id of every row, through a key -> id table in row order, or from the rows still
+// lying partitioned in the workspace
+int assign_build_ids(aqg_ctx* ctx, const AggPlan& p, aqg_groupby* h, const AggBufs& b, uint32_t G) {
     h->build_assigned = false;
-    if (for_build && use_part && n && G && lookup_build) {       // the id of every row through a key -> id table, in row order
-        size_t c = h->reversemap ? h->cap_rows * 4 : 0;
-        AQG_TRY(dev_realloc(ctx, (void**)&h->reversemap, &c, ((size_t)n + 4) * 4));
-        h->cap_rows = c / 4;
+    if (!(p.for_build && p.use_part && p.n && G && (p.lookup_build || b.prows.valid))) return AQG_OK;
+    size_t c = h->reversemap ? h->cap_rows * 4 : 0;
+    AQG_TRY(dev_realloc(ctx, (void**)&h->reversemap, &c, ((size_t)p.n + 4) * 4));
+    h->cap_rows = c / 4;
+    if (p.lookup_build) {
         uint32_t* table;
-        AQG_TRY(aqg_ws_get(ctx, (size_t)lk_D + 64, &table));
-        AQG_HIP(ctx, hipMemsetAsync(table, 0xFF, (size_t)lk_D * 4, ctx->stream));
-        hipLaunchKernelGGL(lookup_fill_kernel, dim3(aqg_grid(ctx, G, 256, 1, 8)), dim3(256), 0, ctx->stream, gt, (const uint32_t*)slot_gid, lk_min, lk_D, table, gt.flags + 8);
-        hipLaunchKernelGGL(lookup_assign_kernel, dim3(aqg_grid(ctx, n / 4 + 1, 256, 1, 8)), dim3(256), 0, ctx->stream, static_cast<const uint32_t*>(ks.col[0]), n, lk_min, lk_D,
-                           (const uint32_t*)table, h->reversemap, gt.flags + 8);
+        AQG_TRY(aqg_ws_get(ctx, (size_t)p.lk_D + 64, &table));
+        AQG_HIP(ctx, hipMemsetAsync(table, 0xFF, (size_t)p.lk_D * 4, ctx->stream));
+        hipLaunchKernelGGL(lookup_fill_kernel, dim3(aqg_grid(ctx, G, 256, 1, 8)), dim3(256), 0, ctx->stream, b.gt, (const uint32_t*)b.slot_gid, p.lk_min, p.lk_D, table, b.gt.flags + 8);
+        hipLaunchKernelGGL(lookup_assign_kernel, dim3(aqg_grid(ctx, p.n / 4 + 1, 256, 1, 8)), dim3(256), 0, ctx->stream, static_cast<const uint32_t*>(p.ks.col[0]), p.n, p.lk_min, p.lk_D,
+                           (const uint32_t*)table, h->reversemap, b.gt.flags + 8);
         AQG_TRY(aqg_check_launch(ctx, "lookup_assign_kernel"));
         uint32_t miss = 0;
-        AQG_HIP(ctx, hipMemcpyAsync(&miss, gt.flags + 8, 4, hipMemcpyDeviceToHost, ctx->stream));
+        AQG_HIP(ctx, hipMemcpyAsync(&miss, b.gt.flags + 8, 4, hipMemcpyDeviceToHost, ctx->stream));
         AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (miss) { h->no_lookup_build = true; return AQG_ERR_RANGE_MISS; }      // a key outside the sampled domain: once more, through the routed form
-        h->build_assigned = true;
         h->plan_bits |= AQG_PLAN_BUILD_PARTITIONED | AQG_PLAN_BUILD_LOOKUP;
-    } else if (for_build && use_part && n && G && prows.valid) {       // the id of every row from the rows still lying partitioned in the workspace
-        size_t c = h->reversemap ? h->cap_rows * 4 : 0;
-        AQG_TRY(dev_realloc(ctx, (void**)&h->reversemap, &c, ((size_t)n + 4) * 4));
-        h->cap_rows = c / 4;
-        AQG_TRY(aqg_partition_assign(ctx, prows, gt, slot_gid, h->reversemap));
-        h->build_assigned = true;
+    } else {
+        AQG_TRY(aqg_partition_assign(ctx, b.prows, b.gt, b.slot_gid, h->reversemap));
         h->plan_bits |= AQG_PLAN_BUILD_PARTITIONED;
     }
+    h->build_assigned = true;
+    return AQG_OK;
+}
+
+int run_agg(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint32_t n, uint32_t hint, bool for_build, aqg_groupby* h,
+            GTable* gt_out, uint32_t** slot_gid_out, uint32_t** occ_out = nullptr, DenseOut* dense_out = nullptr) {
+    AggPlan p;
+    AQG_TRY(make_agg_plan(ctx, ks_in, plan_in, n, hint, for_build, gt_out || slot_gid_out || occ_out, dense_out != nullptr, h, &p));
+    AggBufs b;
+    AQG_TRY(agg_workspace(ctx, p, &b));
+    AQG_TRY(row_pass(ctx, p, h, b));
+    uint32_t G = 0;                                   // (deferred: unknown until the tail is queued)
+    AQG_TRY(read_flags(ctx, p, h, b, &G));
+    // every row its own group: the result is a map of the input (emit_rows_kernel) -- nothing to rank or order
+    const bool row_emit = p.rows_possible && !p.defer && G == n && (p.use_part || p.use_wpart);
+    if (row_emit) h->plan_bits |= AQG_PLAN_ROW_EMIT;
+    SortedParts sparts;
+    AQG_TRY(rank_groups(ctx, p, b, G, row_emit, &sparts));
+    AQG_TRY(emit_outputs(ctx, p, h, b, G, row_emit, sparts));
+    if (p.defer) {
+        uint32_t fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        AQG_HIP(ctx, hipEventSynchronize(ctx->ev_flags));
+        memcpy(fl, b.pinned_flags, 16);
+        AQG_TRY(judge_flags(p, fl, h, &G));
+        ctx->tail_in_flight = true;
+    }
+    AQG_TRY(assign_build_ids(ctx, p, h, b, G));
     h->ngroups = G;
-    if (gt_out) *gt_out = gt;
-    if (dense_out) { dense_out->used = dense; if (dense) dense_out->spec = dspec; }
-    if (slot_gid_out) *slot_gid_out = slot_gid;
-    if (occ_out) *occ_out = occ;
+    if (gt_out) *gt_out = b.gt;
+    if (dense_out) { dense_out->used = p.dense; if (p.dense) dense_out->spec = p.dspec; }
+    if (slot_gid_out) *slot_gid_out = b.slot_gid;
+    if (occ_out) *occ_out = b.occ;
     return AQG_OK;
 }
 
@@ -2057,8 +2131,7 @@ int aqg_groupby_merge_packed(aqg_ctx* ctx, const int64_t* gathered_dev, uint32_t
     h->ctx = ctx;
     const bool int_key = key_dtype == AQG_INT8 || key_dtype == AQG_INT16 || key_dtype == AQG_INT32 || key_dtype == AQG_INT64 || key_dtype == AQG_UINT8 ||
                          key_dtype == AQG_UINT16 || key_dtype == AQG_UINT32 || key_dtype == AQG_UINT64 || key_dtype == AQG_BOOL;
-    static const bool small_merge_off = getenv("AQG_DISABLE_SMALL_MERGE") != nullptr;        // A/B measurements only
-    if (cap_rows <= MERGE_ROWS && int_key && !small_merge_off) {
+    if (cap_rows <= MERGE_ROWS && int_key) {
         // ---- a few small shard tables: one workgroup does the whole merge ------------------------------------------------
         const int mop = op == AQG_RED_COUNT ? AQG_RED_SUM : op;
         int rc = AQG_OK;
@@ -2186,9 +2259,8 @@ __global__ void __launch_bounds__(256) take_rows_kernel(const uint64_t* __restri
 int aqg_grouped_reduce_keyed(aqg_ctx* ctx, aqg_groupby* g, const uint32_t* gid_col, int op, int t, const void* x, void* out_dev) {
     const uint32_t G = g->ngroups, n = g->n;
     // beyond the LDS tables: the build's ids are dense and its group sizes known -- partitioned on the id, direct-indexed (partition1.hip)
-    static const bool gid_off = getenv("AQG_DISABLE_GID_REDUCE") != nullptr;       // A/B measurements only
-    static const uint32_t gid_min = getenv("AQG_GID_MIN") ? (uint32_t)atoi(getenv("AQG_GID_MIN")) : (1u << 16);       // (measured again in round 3, with the value inside the id word: 6.5 against 7.5 ms at 1e5 groups, equal for values that do not pack)
-    if (!gid_off && gid_col == g->reversemap && g->has_counts && G > gid_min && n >= (1u << 22)) {       // (up to ~3e6 groups the one-level hashed plan is as fast: 8.0-8.4 ms against 9.0 per 1e9 rows; 1e7 groups: 17 against 9)
+    constexpr uint32_t GID_MIN = 1u << 16;       // (measured again in round 3, with the value inside the id word: 6.5 against 7.5 ms at 1e5 groups, equal for values that do not pack)
+    if (gid_col == g->reversemap && g->has_counts && G > GID_MIN && n >= (1u << 22)) {       // (up to ~3e6 groups the one-level hashed plan is as fast: 8.0-8.4 ms against 9.0 per 1e9 rows; 1e7 groups: 17 against 9)
         const uint32_t* off = aqg_groupby_offsets(g);
         if (off) {
             const int rc = aqg_gid_reduce(ctx, gid_col, off, g->counts, n, G, op, t, x, out_dev);

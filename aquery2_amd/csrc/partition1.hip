@@ -961,13 +961,12 @@ static bool p1_key_is_column(const KeySpec& ks, int ksz) { return ks.nkeys == 1 
 // integer value columns whose sampled range fits them (at most two), every accumulator over such a column a plain sum / min / max / square
 static int plan_pack(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as, uint32_t n, const ValCols& vc, PackPlan* pp) {
     memset(pp, 0, sizeof *pp);
-    static const bool off = getenv("AQG_DISABLE_PACK") != nullptr;           // A/B measurements only
     if (n < (1u << 22) || !p1_key_is_column(ks, 4) || !(ks.dt[0] == AQG_INT32 || ks.dt[0] == AQG_UINT32)) return AQG_OK;
     KeySpec probe;
     memset(&probe, 0, sizeof probe);
     probe.nkeys = 1; probe.dt[0] = ks.dt[0]; probe.col[0] = ks.col[0];
     int cand[MAXACC], nc = 0;
-    for (int u = 0; u < vc.n && probe.nkeys < MAXKEYS && !off; ++u) {
+    for (int u = 0; u < vc.n && probe.nkeys < MAXKEYS; ++u) {
         if (!(vc.dt[u] == AQG_INT32 || vc.dt[u] == AQG_UINT32)) continue;
         bool ok = true;
         for (int a = 0; a < as.nacc; ++a) if (as.col[a] == vc.col[u] && as.dt[a] != AQG_NONE) ok = ok && as.part[a] == 0 && (as.kind[a] == ACC_ADD_I || as.kind[a] == ACC_MIN || as.kind[a] == ACC_MAX);
@@ -1004,8 +1003,7 @@ static int plan_pack(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as, uint32_
 // the direct-indexed aggregation over range partitions (p1_agg_direct_kernel)
 static void plan_range(const PackPlan& pp, const AccSpec& as, int need_count, uint32_t parts_hashed, RangePlan* rp) {
     memset(rp, 0, sizeof *rp);
-    static const bool off = getenv("AQG_DISABLE_RANGED") != nullptr;         // A/B measurements only
-    if (off || !pp.have_range || pp.key_hi < pp.key_lo) return;
+    if (aqg_switches().disable_ranged || !pp.have_range || pp.key_hi < pp.key_lo) return;
     const long long span = pp.key_hi - pp.key_lo + 1, slack = pp.exact ? 0 : span / 64 + 1024;
     // (the key column is int32 or uint32: its values as 64-bit integers; the bins work on the 32-bit difference to kmin, which wraps correctly)
     const long long lo = pp.key_lo - slack, hi = pp.key_hi + slack;
@@ -1113,8 +1111,7 @@ int aqg_partition1_aggregate(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as,
     // cursors instead of per-chunk histograms, 16384-row tiles with the keys kept in registers, two workgroups per CU so that one tile's
     // loads run under the other's stores (h2o Q5 / Q7 at 1e9 rows, 1e6 groups: this kernel's own 32768-row tiles, one workgroup per CU,
     // moved 3.9 / 2.8 TB/s)
-    static const bool cursor_off = getenv("AQG_DISABLE_P1_CURSORS") != nullptr;             // A/B measurements only
-    if (rp.on && ksz == 4 && nbins <= 256 && !cursor_off) {
+    if (rp.on && ksz == 4 && nbins <= 256 && !aqg_switches().disable_p1_cursors) {
         const uint32_t P = nbins;
         uint32_t *ftot, *fstart, *cur, *seg1, *tp1, *cur1, *seg2, *tp2;
         AQG_TRY(aqg_ws_get(ctx, (size_t)P, &ftot));
@@ -1278,15 +1275,14 @@ int aqg_partition2_aggregate(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as,
         const unsigned hgrid = aqg_grid(ctx, n, 1024, HB, 4);
         if (rp.on) { if constexpr (!K) hipLaunchKernelGGL((p2_hist_kernel<false, true>), dim3(hgrid), dim3(1024), (size_t)P * 4, ctx->stream, static_cast<const uint32_t*>(keycol), n, rp.M, ftot, rp.kmin, rp.D - 1); }
         else hipLaunchKernelGGL((p2_hist_kernel<K>), dim3(hgrid), dim3(1024), (size_t)P * 4, ctx->stream, static_cast<const key_t_<K>*>(keycol), n, P, ftot);
-        static const bool xcd_off = getenv("AQG_DISABLE_XCD_MAP") != nullptr;                   // A/B measurements only
-        const unsigned xgrid = xcd_off ? 0u : ((tiles2 + 7) / 8 * 5 / 4 + 8);                       // workgroups per XCD of the level-2 launch (a quarter of slack)
-        hipLaunchKernelGGL(p2_setup_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)ftot, P, n, (uint32_t)P2_PT, fstart, cur2, seg1, tp1, cur1, seg2, tp2, xcd_off ? (uint32_t*)nullptr : xtp, xgrid);
+        const unsigned xgrid = (tiles2 + 7) / 8 * 5 / 4 + 8;                       // workgroups per XCD of the level-2 launch (a quarter of slack)
+        hipLaunchKernelGGL(p2_setup_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)ftot, P, n, (uint32_t)P2_PT, fstart, cur2, seg1, tp1, cur1, seg2, tp2, xtp, xgrid);
         // the bin of a key word at both levels: the hash or (range partitions) the offset in the domain, scaled to P fine partitions;
         // level 1 takes the coarse partition (fine >> 6), level 2 the fine one inside it (fine & 63)
         const uint32_t scale = rp.on ? rp.M : P;
         P2Level l1{seg1, tp1, cur1, 1u, scale, 6u, 0xFFFFFFFFu, B1, 0u, 0u, rp.kmin, rp.on ? rp.D - 1 : 0u, out.flags + 6};
-        P2Level l2{seg2, tp2, cur2, B1, scale, 0u, 63u, 64u, 64u, pp.kclear, rp.kmin, rp.on ? rp.D - 1 : 0u, out.flags + 6, xcd_off ? (const uint32_t*)nullptr : xtp, xcd_off ? (uint32_t*)nullptr : xtp + 8 * XTP_STRIDE + 32};
-        const unsigned grid2 = xcd_off || 8 * xgrid < tiles2 ? tiles2 : 8 * xgrid;                  // (covers the plain walk too, should the setup decline the map)
+        P2Level l2{seg2, tp2, cur2, B1, scale, 0u, 63u, 64u, 64u, pp.kclear, rp.kmin, rp.on ? rp.D - 1 : 0u, out.flags + 6, xtp, xtp + 8 * XTP_STRIDE + 32};
+        const unsigned grid2 = 8 * xgrid < tiles2 ? tiles2 : 8 * xgrid;                  // (covers the plain walk too, should the setup decline the map)
         auto level = [&](auto mode, auto packing, const key_t_<K>* src, const Planes& pl, const P2Level& lv, unsigned tiles, unsigned tails) -> int {
             constexpr int MODE = decltype(mode)::value;
             constexpr bool PK = decltype(packing)::value;
@@ -1340,7 +1336,7 @@ static WidePlan pw_plan(const KeySpec& ks, const AccSpec& as, uint32_t n, uint32
         if (R > 3u * (uint32_t)w.nt) R = 3u * (uint32_t)w.nt;
         R &= ~7u;
         double mu = (double)R;
-        static const double sigmas = getenv("AQG_PW_SIGMA") ? atof(getenv("AQG_PW_SIGMA")) : 6.0;     // (tests: a small value makes partitions overflow by chance)
+        const double sigmas = aqg_switches().pw_sigma;     // (tests: a small value makes partitions overflow by chance)
         const double mult = hint && hint < n ? (double)n / (double)hint : 1.0;
         for (int it = 0; it < 8; ++it) mu = (double)R - sigmas * sqrt((mu > 1 ? mu : 1) * mult);   // (a million partitions: five sigma leave a quarter of the calls with one partition over)
         if (mu < 64) continue;
@@ -1376,8 +1372,7 @@ size_t aqg_partitionw_ws_bytes(const aqg_ctx* ctx, const KeySpec& ks, uint32_t n
 static bool plan_packw(aqg_ctx* ctx, const KeySpec& ks, uint32_t n, PackW* pk, int* err) {
     memset(pk, 0, sizeof *pk);
     *err = AQG_OK;
-    static const bool off = getenv("AQG_DISABLE_WIDE_PACK") != nullptr;      // A/B measurements only
-    if (off || n < (1u << 22) || ks.nkeys < 3) return false;
+    if (n < (1u << 22) || ks.nkeys < 3) return false;
     for (int k = 0; k < ks.nkeys; ++k) if (!(ks.dt[k] == AQG_INT32 || ks.dt[k] == AQG_UINT32) || ((uintptr_t)ks.col[k] & 15)) return false;
     long long mins[MAXKEYS], maxs[MAXKEYS];
     bool ok = false;
@@ -1442,9 +1437,8 @@ int aqg_partitionw_aggregate(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as,
             k32.col[k] = static_cast<const uint32_t*>(ks.col[k]);
         }
         k32.n = ks.nkeys;
-        static const bool generic_hash = getenv("AQG_PW_GENERIC_HASH") != nullptr;
         memset(&pk, 0, sizeof pk);
-        if (all32 && !generic_hash && pack && *pack) {
+        if (all32 && pack && *pack) {
             int err = AQG_OK;
             packed = plan_packw(ctx, ks, n, &pk, &err);
             AQG_TRY(err);
@@ -1463,14 +1457,14 @@ int aqg_partitionw_aggregate(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as,
         uint32_t shift1 = 0;
         for (int j = 1; j < w.L; ++j) shift1 += (uint32_t)w.low[j - 1];
         const Level1Count lc{cnt, w.P, shift1};
-        level1_counted = all32 && !generic_hash && w.B1 <= 128;
+        level1_counted = all32 && w.B1 <= 128;
         if (level1_counted) AQG_HIP(ctx, hipMemsetAsync(cnt, 0, ((size_t)w.B1 + 1) * 4, ctx->stream));
         if (packed) {
             for (int o = 0; o < pk.nout; ++o) AQG_TRY(aqg_ws_get(ctx, (size_t)n + 64, &pk.out[o]));
             pk.flag = out.flags + 6;
             hipLaunchKernelGGL(pw_hash32_kernel<true>, dim3(aqg_grid(ctx, n / 4 + 1, 256, 2, 16)), dim3(256), 0, ctx->stream, k32, n, seed, h32, pk, lc);
         }
-        else if (all32 && !generic_hash) hipLaunchKernelGGL(pw_hash32_kernel<false>, dim3(aqg_grid(ctx, n / 4 + 1, 256, 2, 16)), dim3(256), 0, ctx->stream, k32, n, seed, h32, pk, lc);
+        else if (all32) hipLaunchKernelGGL(pw_hash32_kernel<false>, dim3(aqg_grid(ctx, n / 4 + 1, 256, 2, 16)), dim3(256), 0, ctx->stream, k32, n, seed, h32, pk, lc);
         else hipLaunchKernelGGL(pw_hash_kernel, dim3(g4), dim3(256), 0, ctx->stream, ks, n, seed, h32);
     }
     if (pack) *pack = packed ? 1 : 0;
@@ -1594,8 +1588,7 @@ int aqg_partitionw_aggregate(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as,
     if (per_cu > 2048u / (unsigned)w.nt) per_cu = 2048u / (unsigned)w.nt;
     if (per_cu < 1) per_cu = 1;
     const unsigned grid = nseg < per_cu * (unsigned)ctx->num_cu ? nseg : per_cu * (unsigned)ctx->num_cu;
-    static const bool defer_off = getenv("AQG_DISABLE_PW_DEFER") != nullptr;                // A/B measurements only
-    if (defer_off) may_defer = false;
+    if (aqg_switches().disable_pw_defer) may_defer = false;
     uint32_t* dwords = nullptr;                                                            // [0] rows of the partitions put off | marks, a byte per partition
     if (may_defer) {
         AQG_TRY(aqg_ws_get(ctx, (size_t)nseg / 4 + 8, &dwords));
@@ -2169,8 +2162,7 @@ static int gid_reduce_impl(aqg_ctx* ctx, const uint32_t* gid, const uint32_t* of
     // a 4-byte integer value column of a narrow sampled range travels INSIDE the id word (ids below 2^24 leave eight bits: h2o v1, v2): one plane per
     // level instead of two.  Every row is verified while it is packed (p2_scatter's PL_PACK); a miss repeats the call with the value as its own plane.
     uint32_t pk_on = 0, pk_shift = 0, pk_min = 0, pk_mask = 0, *pk_flag = nullptr;
-    static const bool pack_off = getenv("AQG_DISABLE_PACK") != nullptr;
-    if (allow_pack && !pack_off && (t == AQG_INT32 || t == AQG_UINT32) && n >= (1u << 22) && ((uintptr_t)x & 15) == 0) {
+    if (allow_pack && (t == AQG_INT32 || t == AQG_UINT32) && n >= (1u << 22) && ((uintptr_t)x & 15) == 0) {
         KeySpec probe;
         memset(&probe, 0, sizeof probe);
         probe.nkeys = 1; probe.dt[0] = t; probe.col[0] = x;

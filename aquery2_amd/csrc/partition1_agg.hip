@@ -516,15 +516,13 @@ __global__ void __launch_bounds__(SB) p1_agg_slot_kernel(const void* __restrict_
 
 // groups one partition's LDS holds, and its key-table capacity, for (ksz, as, need_count)
 static void p1_capacity(int ksz, const AccSpec& as, int need_count, uint32_t* gmax, uint32_t* cap) {
-    static const int lf_env = getenv("AQG_P1_LF1000") ? atoi(getenv("AQG_P1_LF1000")) : 0;
-    const uint32_t lf = lf_env > 0 ? (uint32_t)lf_env : LF1000;
     const double dense = 4.0 + (need_count ? 4.0 : 0.0) + 8.0 * as.nacc;
-    const double slot = (double)(ksz + 2) * 1000.0 / lf;
+    const double slot = (double)(ksz + 2) * 1000.0 / LF1000;
     uint32_t g = (uint32_t)((double)(AGG_LDS - 64) / (dense + slot));
     if (g > 65000) g = 65000;                 // dense ids are 16 bits
     g &= ~3u;
     *gmax = g;
-    *cap = ((uint32_t)((uint64_t)g * 1000 / lf) + 7) & ~7u;
+    *cap = ((uint32_t)((uint64_t)g * 1000 / LF1000) + 7) & ~7u;
 }
 
 // the slot-indexed layout (p1_agg_slot_kernel): slots one partition's LDS holds, and the groups it is planned for (load 0.6)
@@ -541,11 +539,9 @@ static void p1_slot_capacity(int ksz, const AccSpec& as, int need_count, uint32_
 uint32_t aqg_partition_parts(int ksz, const AccSpec& as, int need_count, uint32_t hint, int* layout) {
     if (layout) {
         *layout = AQG_P1_LAYOUT_DENSE_IDS;
-        static const bool slot_off = getenv("AQG_DISABLE_SLOT_LAYOUT") != nullptr;     // A/B measurements only
-        static const int forced = getenv("AQG_P1_BINS") ? atoi(getenv("AQG_P1_BINS")) : 0;
         uint32_t scap, sgroups;
         p1_slot_capacity(ksz, as, need_count, &scap, &sgroups);
-        if (!slot_off && !forced && sgroups >= 256) {
+        if (!aqg_switches().p1_bins && sgroups >= 256) {
             double mu = (double)sgroups;
             for (int it = 0; it < 8; ++it) mu = (double)sgroups - 5.0 * sqrt(mu);
             uint64_t bins = (uint64_t)((double)hint / mu) + 1;
@@ -561,7 +557,7 @@ uint32_t aqg_partition_parts(int ksz, const AccSpec& as, int need_count, uint32_
     if (mu < 16) return 0;
     uint64_t bins = (uint64_t)((double)hint / mu) + 1;
     if (bins < 256) bins = 256;               // every CU gets a partition
-    { static const int forced = getenv("AQG_P1_BINS") ? atoi(getenv("AQG_P1_BINS")) : 0; if (forced > 0) bins = (uint64_t)forced; }   // measurements only
+    if (aqg_switches().p1_bins > 0) bins = (uint64_t)aqg_switches().p1_bins;   // measurements only
     return bins <= (1u << 20) ? (uint32_t)bins : 0;
 }
 

@@ -884,16 +884,13 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
             if (ww == n) return is_max ? run_prefix<T, max_alg<T>, W_MAXP>(ctx, x, n, out) : run_prefix<T, min_alg<T>, W_MINS>(ctx, x, n, out);
             // long windows: van Herk / Gil-Werman over C x 1024 LDS positions (C odd; two arrays of them; two workgroups per CU while
             // they take <= 78 KB and the kernel keeps to 64 VGPRs).  Needs a 16-byte aligned column; others take the doubling kernel.
-            static const bool vh_off = getenv("AQG_DISABLE_VANHERK") != nullptr;
-            static const int vh_c = getenv("AQG_VANHERK_C") ? atoi(getenv("AQG_VANHERK_C")) : 0;
-            if (ww >= 128 && !vh_off && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && n >= 64) {
+            if (ww >= 128 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && n >= 64) {
                 constexpr uint32_t V = 16 / sizeof(T);
                 constexpr int CMAX2 = sizeof(T) <= 4 ? 9 : 3;                           // largest C still run with two workgroups per CU
                 const uint32_t hp = (ww - 1 + V - 1) / V * V;
                 int c = 0;
                 for (int cand : {9, 7, 5, 3}) if (cand <= CMAX2 && (size_t)cand * 2048 * sizeof(T) <= 78 * 1024 && (size_t)cand * 1024 >= 2 * (size_t)hp + V) { c = cand; break; }
                 if (!c) for (int cand : {5, 7, 9, 11}) if ((sizeof(T) <= 4 || cand <= 7) && (size_t)cand * 2048 * sizeof(T) <= 150 * 1024 && (size_t)cand * 1024 >= 2 * (size_t)hp + V) { c = cand; break; }
-                if (vh_c && (size_t)vh_c * 1024 >= (size_t)hp + V && (size_t)vh_c * 2048 * sizeof(T) <= 150 * 1024 && (sizeof(T) <= 4 || vh_c <= 7)) c = vh_c;
                 if (c) {
                     const uint32_t tile_rows = (uint32_t)c * 1024 - hp;
                     const size_t vlds = (size_t)c * 2048 * sizeof(T);

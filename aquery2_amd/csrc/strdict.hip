@@ -141,9 +141,8 @@ extern "C" int aqg_str_encode_sharded(aqg_comm* comm, const char* const* strs_ho
 namespace {
 int str_encode_impl(aqg_ctx* ctx, const char* const* strs_host, uint32_t n, uint32_t* codes_dev, uint32_t* ndistinct_host, std::vector<uint32_t>* first_rows) {
     if (!ctx || (!strs_host && n) || (!codes_dev && n)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_str_encode: bad argument");
-    static const bool host_only = getenv("AQG_STR_HOST") != nullptr;          // A/B measurements only
-    static const uint32_t dev_min = getenv("AQG_STR_DEVICE_MIN") ? (uint32_t)atoi(getenv("AQG_STR_DEVICE_MIN")) : (1u << 16);
-    if (host_only || n < dev_min) return encode_on_host(ctx, strs_host, n, codes_dev, ndistinct_host, first_rows);
+    constexpr uint32_t DEVICE_MIN = 1u << 16;                                  // rows from which the device builds the dictionary
+    if (aqg_switches().str_host || n < DEVICE_MIN) return encode_on_host(ctx, strs_host, n, codes_dev, ndistinct_host, first_rows);
     // ---- host: one walk over the strings, in parallel: lengths, offsets, bytes ---------------------------------------------------
     unsigned nt = std::thread::hardware_concurrency();
     nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
