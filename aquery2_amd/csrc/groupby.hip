@@ -1207,7 +1207,7 @@ constexpr uint64_t PART_LF1000 = 210;
 constexpr unsigned SORTED_EMIT_BLOCK = 1024;
 
 // the row pass of an attempt
-enum class RowPass { STARJOIN, FAST_LDS, DENSE, PART_WIDE, PART_ONE, PART_TWO, PART_ROUND1, HASHED };
+enum class RowPass { STARJOIN, FAST_LDS, FEW_LDS, DENSE, PART_WIDE, PART_ONE, PART_TWO, PART_ROUND1, HASHED };
 
 // every decision of one attempt (make_agg_plan)
 struct AggPlan {
@@ -1396,6 +1396,11 @@ int make_agg_plan(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint3
     p.pass = p.plan.sj ? RowPass::STARJOIN : p.fast ? RowPass::FAST_LDS : p.dense ? RowPass::DENSE : p.use_wpart ? RowPass::PART_WIDE :
              p.p1_bins ? RowPass::PART_ONE : p.p2_parts ? RowPass::PART_TWO : p.use_part ? RowPass::PART_ROUND1 : RowPass::HASHED;
     p.defer = n && (p.pass == RowPass::FAST_LDS || p.pass == RowPass::STARJOIN) && p.small_rank;
+    // the plain call over one 4-byte key and 4-byte values streams its rows by LDS-DMA (groupby_few.hip); builds, callers that take
+    // the table and every other fast shape keep agg32_kernel
+    if (p.pass == RowPass::FAST_LDS && p.defer && !for_build && !table_out && !p.fast_k64 && !p.fast_v8 && as.nacc >= 1 &&
+        aqg_few_fits(as.nacc, p.plan.need_count != 0, p.lcap))
+        p.pass = RowPass::FEW_LDS;
     return AQG_OK;
 }
 
@@ -1552,7 +1557,7 @@ int pass_hashed(aqg_ctx* ctx, const AggPlan& p, const GTable& gt) {
 
 // the plan a row pass stands for in h->plan_bits (the star join has no bit of its own)
 uint32_t row_pass_bits(const AggPlan& p) {
-    constexpr uint32_t bits[] = {0, AQG_PLAN_FAST_LDS, AQG_PLAN_DENSE, AQG_PLAN_PART_WIDE, AQG_PLAN_PART_ONE, AQG_PLAN_PART_TWO, AQG_PLAN_PART_ROUND1};   // (RowPass order)
+    constexpr uint32_t bits[] = {0, AQG_PLAN_FAST_LDS, AQG_PLAN_FAST_LDS, AQG_PLAN_DENSE, AQG_PLAN_PART_WIDE, AQG_PLAN_PART_ONE, AQG_PLAN_PART_TWO, AQG_PLAN_PART_ROUND1};   // (RowPass order)
     if (p.pass == RowPass::HASHED) return p.big_lds ? AQG_PLAN_BIG_LDS : p.use_lds ? AQG_PLAN_SMALL_LDS : AQG_PLAN_HBM_TABLE;
     return bits[(int)p.pass] | (p.sorted_tail ? AQG_PLAN_SORTED_TAIL : 0u);      // (only partition plans order their records)
 }
@@ -1564,6 +1569,9 @@ int row_pass(aqg_ctx* ctx, const AggPlan& p, aqg_groupby* h, AggBufs& b) {
         switch (p.pass) {
         case RowPass::STARJOIN: AQG_TRY(pass_starjoin(ctx, p, b.gt)); break;
         case RowPass::FAST_LDS: AQG_TRY(pass_fast(ctx, p, b.gt)); break;
+        case RowPass::FEW_LDS:
+            AQG_TRY(aqg_few_aggregate(ctx, static_cast<const uint32_t*>(p.ks.col[0]), p.plan.as.nacc, p.plan.need_count != 0, p.fv, b.gt, p.n, p.lcap));
+            break;
         case RowPass::DENSE: AQG_TRY(aqg_dense_aggregate(ctx, p.ks, p.dspec, p.plan.as, p.n, p.plan.need_count, b.gt)); break;
         case RowPass::HASHED: AQG_TRY(pass_hashed(ctx, p, b.gt)); break;
         default: AQG_TRY(pass_partitions(ctx, p, h, b));

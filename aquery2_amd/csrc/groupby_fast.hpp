@@ -12,3 +12,8 @@ constexpr uint32_t OCCUPIED = 0xFFFFFFFEu;   // first_row mark: "group exists, f
 // merged into gt.  Records the kernel's duration in the context's kernel timer.
 int aqg_fast_aggregate(aqg_ctx* ctx, const uint32_t* keys, const uint32_t* keys_hi, bool k64, bool v8, int nacc, bool need_count,
                        const FastVals& fv, GTable gt, uint32_t n, uint32_t lcap, size_t lds, unsigned grid, unsigned block);
+
+// the same pass for one 4-byte key column and 1-4 accumulators over 4-byte value columns, all 16-byte aligned
+// (groupby_few.hip): the rows stream through LDS by DMA.  aqg_few_fits: its LDS (ring + a table of lcap slots) fits a CU.
+bool aqg_few_fits(int nacc, bool need_count, uint32_t lcap);
+int aqg_few_aggregate(aqg_ctx* ctx, const uint32_t* keys, int nacc, bool need_count, const FastVals& fv, GTable gt, uint32_t n, uint32_t lcap);
