@@ -25,6 +25,7 @@ TAG2NP = {
 NP2TAG = {v: k for k, v in TAG2NP.items() if k != BOOL}
 NP2TAG[np.dtype(np.bool_)] = BOOL
 VEC_VEC, VEC_SCALAR, SCALAR_VEC = 0, 1, 2
+ORDER_ASC, ORDER_DESC, ORDER_NEG = 0, 1, 2
 PLAN_FAST_LDS, PLAN_SMALL_LDS, PLAN_BIG_LDS, PLAN_DENSE, PLAN_PART_ONE, PLAN_PART_TWO, PLAN_PART_ROUND1, PLAN_PART_WIDE, PLAN_SORTED_TAIL, PLAN_HBM_TABLE, PLAN_BUILD_PARTITIONED, PLAN_GID_PARTITION, PLAN_PACKED_VALUES, PLAN_RANGE_PARTITIONS, PLAN_ROW_EMIT, PLAN_PACKED_KEYS, PLAN_BUILD_LOOKUP = (1 << i for i in range(17))
 
 
@@ -534,6 +535,28 @@ class Device:
         self._chk(self.lib.aqg_mask_to_index(self.ctx, C.c_void_p(md.ptr), C.c_uint32(md.n), C.c_void_p(out.ptr), C.byref(m)),
                   "aqg_mask_to_index")
         return out.to_host()[:m.value].copy()
+
+    # -- sort
+    def sort_rows(self, keys, orders, rows=None, out=None, keep=False):
+        """aqg_sort_rows: np.uint32 row ids ordered by `keys` (key 0 most significant; numpy arrays or DevBufs of one length n)
+        under `orders` (ORDER_ASC / ORDER_DESC / ORDER_NEG per key), stable.  `rows`: the row ids to order (repeats allowed),
+        default every row.  `out`: a DevBuf to write into (it may be `rows` itself); keep=True returns the DevBuf."""
+        kd, dts, ptrs = self._keyargs(keys)
+        n = kd[0].n if kd else 0
+        rd = None if rows is None else self._dev(np.ascontiguousarray(rows, dtype=np.uint32) if not isinstance(rows, DevBuf) else rows)
+        m = n if rd is None else rd.n
+        if out is None:
+            out = self.empty(m, np.uint32)
+        oa = (C.c_int * max(1, len(orders)))(*orders)
+        self._chk(self.lib.aqg_sort_rows(self.ctx, len(kd), dts, ptrs, oa, C.c_uint32(n), C.c_void_p(rd.ptr) if rd is not None else None,
+                                         C.c_uint32(m), C.c_void_p(out.ptr)), "aqg_sort_rows")
+        return out if keep else out.to_host()
+
+    def sort_last_passes(self):
+        """digit passes the last sort_rows on this device ran (skipped digit positions not counted)"""
+        p = C.c_uint32()
+        self._chk(self.lib.aqg_sort_last_passes(self.ctx, C.byref(p)), "aqg_sort_last_passes")
+        return p.value
 
     # -- group by
     def _keyargs(self, keys):

@@ -46,6 +46,10 @@ struct aqg_ctx {
     hipEvent_t ev_fetch = nullptr;
     uint32_t pin_chunks[3] = {0, 0, 0};          // chunks of the last aqg_col_pin upload: page-locked + DMA / staged through pinned buffers / plain pageable copy
     std::unordered_map<const void*, int> max_lds;   // largest dynamic LDS size already granted per kernel (aqg_allow_lds)
+    // aqg_sort_rows: digit passes of the last call (host), or in sort_passes_dev when the one-workgroup sort ran
+    uint32_t sort_passes = 0;
+    bool sort_passes_on_dev = false;
+    uint32_t* sort_passes_dev = nullptr;
     // pinned host staging for small results
     void* host_stage = nullptr;
     size_t host_stage_cap = 0;

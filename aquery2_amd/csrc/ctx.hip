@@ -105,6 +105,7 @@ void aqg_ctx_destroy(aqg_ctx* ctx) {
     for (int k = 0; k < 2; ++k) { if (ctx->up_buf[k]) hipHostFree(ctx->up_buf[k]); if (ctx->up_ev[k]) hipEventDestroy(ctx->up_ev[k]); }
     if (ctx->ws) hipFree(ctx->ws);
     if (ctx->rank_bm) hipFree(ctx->rank_bm);
+    if (ctx->sort_passes_dev) hipFree(ctx->sort_passes_dev);
     for (auto& e : ctx->pool) hipFree(e.first);
     if (ctx->pool_big) hipFree(ctx->pool_big);
     if (ctx->host_stage) hipHostFree(ctx->host_stage);

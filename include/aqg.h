@@ -181,6 +181,21 @@ int aqg_compact(aqg_ctx* ctx, int t, const void* x, const uint8_t* mask, uint32_
 /* row ids of set mask entries, ascending (selection vector for multi-column filters) */
 int aqg_mask_to_index(aqg_ctx* ctx, const uint8_t* mask, uint32_t n, uint32_t* idx_out, uint32_t* m_host);
 
+/* ---- sort --------------------------------------------------------------------
+ * TableInfo::order_by  server/table.h:447-465 (a host std::sort over a tuple comparator there).
+ * keys[j]: device columns of n rows, key 0 most significant; INT8/16/32/64/128, UINT8/16/32/64/128, BOOL, FLOAT, DOUBLE
+ * (other dtypes: AQG_ERR_DTYPE, nothing written).  rows_in: m device row ids below n, repeats allowed; NULL = identity, m == n.
+ * rows_out receives m ids; it may equal or overlap rows_in and must not overlap a key column.  STABLE: ties keep the order of rows_in.
+ * ASC / DESC: ascending / descending value.  NEG: ascending two's-complement negation in the key's own width (the header
+ * layer's `-col[i]` key of unsigned 32/64/128-bit columns: 0 first, the rest descending); not for floating keys (AQG_ERR_ARG).
+ * Floating keys: -0.0 == +0.0 (the next key or the input order breaks the tie); every NaN is one key, after +inf under ASC,
+ * before it under DESC.  1 <= nkeys <= 8.  Asynchronous, scratch from the context workspace.                     */
+enum { AQG_ORDER_ASC = 0, AQG_ORDER_DESC = 1, AQG_ORDER_NEG = 2 };
+int aqg_sort_rows(aqg_ctx* ctx, int nkeys, const int* key_dtypes, const void* const* keys, const int* orders,
+                  uint32_t n, const uint32_t* rows_in, uint32_t m, uint32_t* rows_out);
+/* digit passes the last aqg_sort_rows on this context actually ran (skipped passes not counted) */
+int aqg_sort_last_passes(aqg_ctx* ctx, uint32_t* passes_host);
+
 /* ---- hash group-by -----------------------------------------------------------
  * Replaces AQHashTable (server/hasher.h:146-199) + set::hashtable_push
  * (server/unordered_dense.h:1117-1147) + HashTableFactory::get (:327-357).

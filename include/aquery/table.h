@@ -303,18 +303,45 @@ struct TableInfo {
         materialize<0>(idxs, tbl);
         return tbl;
     }
-    // order_by<c0, c1, ...>: row ids sorted by the listed columns (column c >= 0 ascending; -1 - c descending), std::sort on
-    // the host like the reference (not stable, ties in unspecified order)
+    // order_by<c0, c1, ...>: row ids sorted by the listed columns (column c >= 0 ascending; -1 - c by `-col[i]`, the reference's
+    // descending key).  When every listed column has a device type, one STABLE (ties keep the order of `ord`, or of the rows)
+    // aqg_sort_rows call orders the ids on the device (`-col[i]` is DESC, or NEG for unsigned int / long / __int128, whose negation
+    // stays unsigned: 0 first, then descending).  Other column types keep the host std::sort of the reference (ties in unspecified
+    // order there).
     template <int... ocols>
     inline vector_type<uint32_t>* order_by(vector_type<uint32_t>* ord = nullptr) {
         const uint32_t n = rows();
-        if (!ord) {
-            ord = new vector_type<uint32_t>(n);
-            for (uint32_t i = 0; i < n; ++i) (*ord)[i] = i;
+        if constexpr (sizeof...(ocols) > 0 && (aq::dev::on_device<std::tuple_element_t<(size_t)(ocols >= 0 ? ocols : -1 - ocols), tuple_type>> && ...)) {
+            auto& rt = aq::dev::Runtime::get();
+            constexpr int nk = (int)sizeof...(ocols);
+            int dts[nk], ords[nk];
+            const void* ptrs[nk];
+            std::vector<std::unique_ptr<aq::dev::In>> ins;
+            order_bind<ocols...>(dts, ords, ptrs, ins);
+            const bool given = ord != nullptr;
+            const uint32_t m = given ? ord->size : n;
+            if (!given) ord = new vector_type<uint32_t>(n);
+            if (m == 0) return ord;
+            std::unique_ptr<aq::dev::In> rin;
+            if (given) rin = std::make_unique<aq::dev::In>(ord->container, (size_t)m * 4, false);
+            void* dout = nullptr;
+            aq::dev::check(aqg_malloc(rt.ctx(), (size_t)m * 4, &dout), "aqg_malloc");
+            aq::dev::check(aqg_sort_rows(rt.ctx(), nk, dts, ptrs, ords, n, rin ? static_cast<const uint32_t*>(rin->d) : nullptr, m,
+                                         static_cast<uint32_t*>(dout)), "aqg_sort_rows");
+            aq::dev::check(aqg_d2h(rt.ctx(), ord->container, dout, (size_t)m * 4), "aqg_d2h");
+            aqg_free(rt.ctx(), dout);
+            // `*ord` belongs to the caller, who may rewrite it on the host: no device mirror of the new ids is kept, and a mirror of
+            // the ids it held before (a device result it came from) is dropped
+            rt.forget_range(ord->container, (size_t)m * 4);
+        } else {
+            if (!ord) {
+                ord = new vector_type<uint32_t>(n);
+                for (uint32_t i = 0; i < n; ++i) (*ord)[i] = i;
+            }
+            std::sort(ord->begin(), ord->end(), [this](const uint32_t& l, const uint32_t& r) {
+                return std::make_tuple(order_key<ocols>(l)...) < std::make_tuple(order_key<ocols>(r)...);
+            });
         }
-        std::sort(ord->begin(), ord->end(), [this](const uint32_t& l, const uint32_t& r) {
-            return std::make_tuple(order_key<ocols>(l)...) < std::make_tuple(order_key<ocols>(r)...);
-        });
         return ord;
     }
     template <int... ocols> auto order_by_view();
@@ -385,6 +412,23 @@ private:
     template <int c> auto order_key(uint32_t i) {
         if constexpr (c >= 0) return std::get<(size_t)c>(cols)[i];
         else return -std::get<(size_t)(-1 - c)>(cols)[i];
+    }
+    template <int... ocols> void order_bind(int* dts, int* ords, const void** ptrs, std::vector<std::unique_ptr<aq::dev::In>>& ins) {
+        int j = 0;
+        ((void)([&] {
+            constexpr size_t c = (size_t)(ocols >= 0 ? ocols : -1 - ocols);
+            using T = std::remove_cv_t<std::tuple_element_t<c, tuple_type>>;
+            constexpr bool neg_unsigned = std::is_same_v<T, unsigned int> || std::is_same_v<T, unsigned long> || std::is_same_v<T, unsigned long long>
+#ifdef __SIZEOF_INT128__
+                                          || std::is_same_v<T, unsigned __int128>
+#endif
+                ;
+            auto& col = std::get<c>(cols);
+            dts[j] = aq::dev::tag_of<T>::value;
+            ords[j] = ocols >= 0 ? AQG_ORDER_ASC : neg_unsigned ? AQG_ORDER_NEG : AQG_ORDER_DESC;
+            ins.push_back(std::make_unique<aq::dev::In>(col.container, (size_t)col.size * sizeof(T), col.capacity == 0));
+            ptrs[j++] = ins.back()->d;
+        }()), ...);
     }
     template <size_t... Is> tuple_type row_tuple(uint32_t i, std::index_sequence<Is...>) { return tuple_type(std::get<Is>(cols)[i]...); }
     template <size_t... Is> void distinct_bind(int* dts, const void** ptrs, std::vector<std::unique_ptr<aq::dev::In>>& ins, std::index_sequence<Is...>) {
