@@ -1317,7 +1317,7 @@ int make_agg_plan(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint3
         ks.wide = 1;
         for (int j = 0; j < ks.nkeys; ++j) ks.shift[j] = 0;
     }
-    // A BUILD above the LDS tables takes the partition plans too (partition1.hip: the group table with counts, then one more pass over the
+    // A BUILD above the LDS tables takes the partition plans too (partition1.hip, partition_assign.hip: the group table with counts, then one more pass over the
     // partitioned rows for the id of every row) instead of inserting every row into an HBM table and looking every row up again
     p.build_part = for_build && !sw.disable_build_partition && !ks.wide && n >= (1u << 20) && hint > 3072 && hint <= (1u << 25) && hint < sw.sorted_tail_min;
     if (p.build_part) p.plan.need_count = 1;          // the group sizes come out of the partition aggregation
@@ -2266,7 +2266,7 @@ __global__ void __launch_bounds__(256) take_rows_kernel(const uint64_t* __restri
 // of the flat layout -- segscan.hip) through the ordinary group-by plans; ids appear in first-occurrence order, so group g is result g
 int aqg_grouped_reduce_keyed(aqg_ctx* ctx, aqg_groupby* g, const uint32_t* gid_col, int op, int t, const void* x, void* out_dev) {
     const uint32_t G = g->ngroups, n = g->n;
-    // beyond the LDS tables: the build's ids are dense and its group sizes known -- partitioned on the id, direct-indexed (partition1.hip)
+    // beyond the LDS tables: the build's ids are dense and its group sizes known -- partitioned on the id, direct-indexed (partition_wide.hip)
     constexpr uint32_t GID_MIN = 1u << 16;       // (measured again in round 3, with the value inside the id word: 6.5 against 7.5 ms at 1e5 groups, equal for values that do not pack)
     if (gid_col == g->reversemap && g->has_counts && G > GID_MIN && n >= (1u << 22)) {       // (up to ~3e6 groups the one-level hashed plan is as fast: 8.0-8.4 ms against 9.0 per 1e9 rows; 1e7 groups: 17 against 9)
         const uint32_t* off = aqg_groupby_offsets(g);

@@ -1,4 +1,4 @@
-// partition1.hpp -- host entry points of the partition plans of partition1.hip, called by run_agg (groupby.hip)
+// partition1.hpp -- host entry points of the partition plans (partition1.hip, partition_wide.hip, sorted_tail.hip, partition_assign.hip), called by run_agg (groupby.hip)
 #pragma once
 #include "groupby_dev.hpp"
 

@@ -1,6 +1,6 @@
-// partition1_int.hpp -- what partition1.hip (histograms, scatters, the plans' hosts) and partition1_agg.hip (the per-partition aggregation
-// kernels and their launchers) share.  Two translation units only because the aggregation kernels are ~90 large instantiations: hipcc takes
-// three minutes for them, and the build runs them beside the scatters instead of behind them.
+// partition1_int.hpp -- what the partition plans (partition1.hip, partition_wide.hip, sorted_tail.hip, partition_assign.hip), the
+// tile scatter they move rows with (tile_scatter.hip) and partition1_agg.hip (the per-partition aggregation kernels and their launchers) share:
+// the key word, the accumulator operand codes, the value-column and packing plans, and the launchers one file offers another.
 #pragma once
 #include <cmath>
 #include "groupby_dev.hpp"
@@ -42,7 +42,16 @@ constexpr uint32_t LF1000 = 500;    // load factor of the key table
 
 // the distinct value columns of the accumulators (an accumulator over the row index has none)
 struct ValCols { int n; const void* col[MAXACC]; int dt[MAXACC]; int of_acc[MAXACC]; };
-// which value columns travel inside the key word (PackSpec, partition1.hip) and the sampled range of the key column
+static inline void p1_val_cols(const AccSpec& as, ValCols* vc) {
+    vc->n = 0;
+    for (int a = 0; a < as.nacc; ++a) {
+        vc->of_acc[a] = -1;
+        if (as.dt[a] == AQG_NONE) continue;
+        for (int u = 0; u < vc->n; ++u) if (vc->col[u] == as.col[a]) vc->of_acc[a] = u;
+        if (vc->of_acc[a] < 0) { vc->col[vc->n] = as.col[a]; vc->dt[vc->n] = as.dt[a]; vc->of_acc[a] = vc->n++; }
+    }
+}
+// which value columns travel inside the key word (PackSpec, tile_scatter.hpp) and the sampled range of the key column
 struct PackPlan { int n; const void* col[2]; uint32_t min[2], shift[2], fmask[2]; uint32_t kmax, kclear; bool have_range, exact; long long key_lo, key_hi; };
 static inline int pack_field_of(const PackPlan& pp, const void* col) { for (int f = 0; f < pp.n; ++f) if (pp.col[f] == col) return f; return -1; }
 // range partitions over a dense key domain (p1_agg_direct_kernel)
@@ -56,3 +65,5 @@ int p1_launch_agg(aqg_ctx* ctx, int ksz, const AccSpec& as, const ValCols& vc, c
                   const PackPlan* pp = nullptr, int layout = AQG_P1_LAYOUT_DENSE_IDS);
 int p1_launch_agg_direct(aqg_ctx* ctx, const AccSpec& as, const ValCols& vc, const void* pkeys, const void* prows, void* const* pvals,
                          const uint32_t* pstart, uint32_t pstride, uint32_t n, int need_count, GTable out, uint32_t out_cap, const PackPlan* pp, const RangePlan& rp);
+// pstart / pfirst of the PP order-preserving partitions of the dense ids 0 .. G-1 (partition_wide.hip; offsets == nullptr: the identity)
+void aqg_gid_setup(aqg_ctx* ctx, const uint32_t* offsets, uint32_t G, uint32_t M, uint32_t PP, uint32_t* pstart, uint32_t* pfirst);
