@@ -116,6 +116,26 @@ static inline void aqg_pool_give(aqg_ctx* ctx, void* p, size_t cap) {
     }
     (void)hipFree(p);
 }
+// `need` bytes from the pool, else from hipMalloc (*err: its status); nullptr, and no error left behind for the next launch check, when there is no memory
+static inline void* aqg_pool_alloc(aqg_ctx* ctx, size_t need, size_t* cap, hipError_t* err = nullptr) {
+    if (void* q = aqg_pool_take(ctx, need, cap)) return q;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, need);
+    if (err) *err = e;
+    if (e != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    *cap = need;
+    return q;
+}
+// grow-only device buffer of a handle: *p holds at least `need` bytes afterwards (its contents are not kept)
+template <class T> static inline int aqg_dev_realloc(aqg_ctx* ctx, T** p, size_t* cap, size_t need) {
+    if (need <= *cap && *p) return AQG_OK;
+    if (*p) { aqg_pool_give(ctx, *p, *cap); *p = nullptr; *cap = 0; }        // (stream-ordered reuse; a buffer too large for the pool is freed, which synchronises)
+    hipError_t e = hipSuccess;
+    void* q = aqg_pool_alloc(ctx, need < 256 ? 256 : need, cap, &e);
+    if (!q) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return AQG_ERR_NOMEM; }
+    *p = static_cast<T*>(q);
+    return AQG_OK;
+}
 int aqg_ws_alloc(aqg_ctx* ctx, size_t bytes, void** out);
 int aqg_ws_ensure(aqg_ctx* ctx, size_t bytes);
 template <class T> static inline int aqg_ws_get(aqg_ctx* ctx, size_t count, T** out) {
@@ -135,7 +155,7 @@ struct aqg_groupby;
 size_t aqg_postproc_ws_bytes(uint32_t n, uint32_t G, int esz);
 int aqg_radix_by_group(aqg_ctx* ctx, aqg_groupby* g, uint32_t* row_ids_dev, const void* x, int esz, void* xout, bool ws_managed);
 int aqg_group_offsets(aqg_ctx* ctx, const aqg_groupby* g, uint32_t* offsets_dev, uint32_t* bsum);
-// groupby.hip: out[g] = op(x[rows whose id in gid_col is g]) through the group-by plans (gid_col: n dense ids in first-occurrence order)
+// grouped_reduce.hip: out[g] = op(x[rows whose id in gid_col is g]) through the group-by plans (gid_col: n dense ids in first-occurrence order)
 extern "C" int aqg_grouped_reduce_keyed(aqg_ctx* ctx, aqg_groupby* g, const uint32_t* gid_col, int op, int t, const void* x, void* out_dev);
 
 // exchange.hip: the all-gather of a communicator (`bytes` bytes of every rank, rank order, on / ordered behind the context's stream)

@@ -20,6 +20,12 @@ __host__ __device__ static inline aqg_i128 i128_add(aqg_i128 a, aqg_i128 b) {
     r.hi = a.hi + b.hi + (r.lo < a.lo ? 1ull : 0ull);
     return r;
 }
+__device__ static inline aqg_i128 i128_mul(aqg_i128 a, aqg_i128 b) {   // low 128 bits of the product (two's complement: sign-agnostic)
+    aqg_i128 r;
+    r.lo = a.lo * b.lo;
+    r.hi = __umul64hi(a.lo, b.lo) + a.lo * b.hi + a.hi * b.lo;
+    return r;
+}
 
 // correctly rounded (nearest-even) conversions of 128-bit integers to double
 __device__ static inline double u128_to_double(uint64_t hi, uint64_t lo) {

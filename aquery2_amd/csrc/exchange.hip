@@ -206,7 +206,6 @@ __device__ inline aqg_i128 join_halves(const void* lo, const void* hi, uint32_t 
     const aqg_i128 l = static_cast<const aqg_i128*>(lo)[g], h = static_cast<const aqg_i128*>(hi)[g];
     return {l.lo, h.lo + l.hi};
 }
-__device__ inline aqg_i128 xmul_128(aqg_i128 a, aqg_i128 b) { return {a.lo * b.lo, __umul64hi(a.lo, b.lo) + a.lo * b.hi + a.hi * b.lo}; }
 __device__ __noinline__ static void copy_element(void* __restrict__ dst_col, const void* __restrict__ src_col, size_t g, int size) {
     const unsigned char* src = static_cast<const unsigned char*>(src_col) + g * size;
     unsigned char* dst = static_cast<unsigned char*>(dst_col) + g * size;
@@ -226,7 +225,7 @@ __global__ void __launch_bounds__(256) xfinal_kernel(FinalSpec fs, uint32_t G) {
                 const double s = fp ? static_cast<const double*>(fs.a[j])[g] : to_double(int_sum());
                 store_at<double>(fs.out[j], g, s / (double)cn.lo);
             } break;
-            case AQG_RED_VAR: case AQG_RED_STDDEV: {                          // (ssq - s*s/(double)(n+1)) / (double)(n+1), as emit_record (groupby.hip)
+            case AQG_RED_VAR: case AQG_RED_STDDEV: {                          // (ssq - s*s/(double)(n+1)) / (double)(n+1), as emit_record_from (groupby_tail.hip)
                 const double np1 = (double)(static_cast<const aqg_i128*>(fs.b[j])[g].lo + 1);
                 double d;
                 if (fp) {
@@ -234,7 +233,7 @@ __global__ void __launch_bounds__(256) xfinal_kernel(FinalSpec fs, uint32_t G) {
                     d = (qq - sd * sd / np1) / np1;
                 } else {
                     const aqg_i128 sm = int_sum(), qq = join_halves(fs.q[j], fs.q_hi[j], g);
-                    const aqg_i128 ss = xmul_128(sm, sm);                     // s * s in the 128-bit LongType (wraps like the reference)
+                    const aqg_i128 ss = i128_mul(sm, sm);                     // s * s in the 128-bit LongType (wraps like the reference)
                     d = (to_double(qq) - to_double(ss) / np1) / np1;
                 }
                 store_at<double>(fs.out[j], g, fs.op[j] == AQG_RED_STDDEV ? sqrt(d) : d);
@@ -377,8 +376,8 @@ __global__ void __launch_bounds__(1024) xmerge_small_kernel(const uint64_t* __re
     if (threadIdx.x == 0) { sm.info[0] = G; sm.info[1] = s_bad; }
 }
 
-// Key columns that are not plain integers travel as the NORMALISED integer columns the local group-by made of them (groupby.hip
-// normalize_keys): date_t -> uint32, time_t -> uint64 (padding byte cleared), timestamp_t -> {uint32 date, uint64 time}, 128-bit integers
+// Key columns that are not plain integers travel as the NORMALISED integer columns the local group-by made of them (groupby_keys.hip
+// aqg_normalize_keys): date_t -> uint32, time_t -> uint64 (padding byte cleared), timestamp_t -> {uint32 date, uint64 time}, 128-bit integers
 // -> {low, high}.  The layout depends on the key dtypes alone, so every rank -- one whose local call failed too -- sizes the payload alike.
 // Floating keys (their NaN rows are numbered by LOCAL row) and strings (codes of a per-rank dictionary: aqg_str_encode_sharded makes global
 // ones) are not offered here.

@@ -1,4 +1,4 @@
-// groupby_dev.hpp -- device-side vocabulary shared by groupby.hip and partition.hip: key packing, accumulator operands,
+// groupby_dev.hpp -- device-side vocabulary shared by the group-by plans (groupby*.hip, dense.hip, the partition files): key packing, accumulator operands,
 // the open-addressing table record layout and its find/insert primitives.
 #pragma once
 #include "aqg_internal.hpp"
@@ -85,6 +85,20 @@ __device__ inline uint64_t map_i(int64_t v) { return (uint64_t)v ^ 0x80000000000
 __device__ inline int64_t unmap_i(uint64_t u) { return (int64_t)(u ^ 0x8000000000000000ull); }
 __device__ inline uint64_t map_f(double d) { uint64_t b = __builtin_bit_cast(uint64_t, d); return (b >> 63) ? ~b : (b | 0x8000000000000000ull); }
 __device__ inline double unmap_f(uint64_t u) { uint64_t b = (u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u; return __builtin_bit_cast(double, b); }
+
+// a MIN / MAX accumulator (order-preserving map) -> element g of a result column of T
+// (not inlined: a size / dtype switch whose arms STORE, inlined into a loop with a 64-bit value live across it, is the shape hipcc
+// 7.2 miscompiled in unpack_kernel -- profiles/r2_hipcc_switch_miscompile.md)
+template <class T> __device__ __noinline__ void store_minmax(void* out, uint32_t g, uint64_t mapped, bool is_max) {
+    T v;
+    if constexpr (std::is_floating_point_v<T>) {
+        double d = unmap_f(mapped);
+        v = (T)d;
+        if (is_max) { T seed = dlimits<T>::min(); v = seed > v ? seed : v; }   // max seeds with numeric_limits<T>::min() (D8)
+    } else if constexpr (std::is_unsigned_v<T>) v = (T)mapped;
+    else v = (T)unmap_i(mapped);
+    static_cast<T*>(out)[g] = v;
+}
 
 __host__ __device__ inline int vclass(int dt) {
     switch (dt) {

@@ -1,6 +1,6 @@
 // groupby_fast.hip -- the fast LDS group-by kernel: one or two 4-byte keys or one 8-byte key, up to four accumulators over
 // 4- and 8-byte value columns (h2o Q1, Q4 and most few-group shapes; the first pass of aqg_groupby_build).  Planner, table
-// layout and everything downstream: groupby.hip.  Replaces the hash-table build + per-group loop of the reference for these
+// layout: groupby.hip; everything downstream: groupby_tail.hip.  Replaces the hash-table build + per-group loop of the reference for these
 // shapes (server/hasher.h:146-199, engine/ast.py:722-789).
 #include "groupby_fast.hpp"
 

@@ -1,4 +1,4 @@
-// groupby_fast.hpp -- the fast LDS group-by kernel (groupby_fast.hip) as seen by the planner in groupby.hip
+// groupby_fast.hpp -- the fast LDS group-by kernel (groupby_fast.hip) as seen by the planner (groupby.hip) and the tail (groupby_tail.hip)
 #pragma once
 #include "groupby_dev.hpp"
 

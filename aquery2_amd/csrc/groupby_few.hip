@@ -1,7 +1,7 @@
 // groupby_few.hip -- the row pass of the fast LDS group-by for its most common shape: one 4-byte key column, one to four
 // accumulators over 4-byte value columns (int32 / uint32 / float), a table that fits LDS_SMALL (h2o Q1).  Every other fast
 // shape keeps agg32_kernel (groupby_fast.hip); the table layout, the merge into the group table and everything downstream are
-// the same (groupby.hip).
+// the same (groupby.hip, groupby_tail.hip).
 //
 // agg32_kernel reads its rows with plain 16-byte loads and tops out at ~5.7-5.8 TB/s however they are issued.  Here every wave
 // streams its share of the workgroup's span through a ring of its own in LDS by global_load_lds_dwordx4 with the nt policy,

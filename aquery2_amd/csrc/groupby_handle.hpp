@@ -1,4 +1,4 @@
-// groupby_handle.hpp -- the opaque aqg_groupby handle (shared by groupby.hip and postproc.hip)
+// groupby_handle.hpp -- the opaque aqg_groupby handle (shared by the groupby*.hip files, grouped_reduce.hip, segscan.hip and postproc.hip)
 #pragma once
 #include <cstddef>
 #include <cstdint>

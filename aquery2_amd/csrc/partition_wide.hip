@@ -15,7 +15,7 @@ namespace {
 // a partition has ~1000 ROWS (pw_plan).  The key columns travel as ordinary dword planes.  pw_agg then loads a whole partition into LDS
 // and groups it there: an open-addressing table of representative row indices, tuples compared LDS to LDS, accumulators indexed by
 // the representative.  The record's key word is the group's first row: emit fetches the key columns through it (the wide-tuple
-// convention of groupby.hip).  Sized by rows, not by groups: a tuple that dominates the input overflows its partition and the call
+// convention of groupby_hashed.hip / groupby_tail.hip).  Sized by rows, not by groups: a tuple that dominates the input overflows its partition and the call
 // falls back to the HBM table.
 __device__ inline uint32_t pw_seeded(uint32_t h, uint32_t seed) { h ^= seed; h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; return h ^ (h >> 16); }
 __global__ void __launch_bounds__(256) pw_hash_kernel(KeySpec ks, uint32_t n, uint32_t seed, uint32_t* __restrict__ out) {
@@ -577,12 +577,6 @@ __global__ void __launch_bounds__(256) gid_setup_kernel(const uint32_t* __restri
     }
 }
 
-__device__ inline aqg_i128 mul_128_p1(aqg_i128 a, aqg_i128 b) {   // low 128 bits of the product (two's complement: sign-agnostic)
-    aqg_i128 r;
-    r.lo = a.lo * b.lo;
-    r.hi = __umul64hi(a.lo, b.lo) + a.lo * b.hi + a.hi * b.lo;
-    return r;
-}
 struct GidAgg {
     const uint32_t* gid; const void* val; int vdt; int op;
     const uint32_t* pstart; const uint32_t* pfirst; const uint32_t* counts;
@@ -604,13 +598,6 @@ __device__ inline uint64_t gid_operand(const GidAgg& a, size_t i, int kind, int 
     case AQG_UINT64: return val_operand_t(static_cast<const uint64_t*>(a.val)[i], kind, square);
     default: return val_operand_t(static_cast<const double*>(a.val)[i], kind, square);
     }
-}
-template <class T> __device__ __noinline__ void gid_store_minmax(void* out, uint32_t g, uint64_t mapped, bool is_max) {
-    T v;
-    if constexpr (std::is_floating_point_v<T>) { v = (T)unmap_f(mapped); if (is_max) { T seed = dlimits<T>::min(); v = seed > v ? seed : v; } }   // (D8: max seeds with numeric_limits<T>::min())
-    else if constexpr (std::is_unsigned_v<T>) v = (T)mapped;
-    else v = (T)unmap_i(mapped);
-    static_cast<T*>(out)[g] = v;
 }
 // V8: 8-byte values.  A lane takes GR consecutive rows of a step by 16-byte loads (4-byte aligned: a partition starts anywhere) and the next
 // step's rows are in flight while this step's are accumulated -- with four rows per lane and step by dword loads, one step at a time, the
@@ -722,7 +709,7 @@ __global__ void __launch_bounds__(1024, 8) gid_agg_kernel(GidAgg a) {      // (e
                 else {
                     const aqg_i128 sm = vc == VC_U ? i128_from_u64(s) : i128_from_i64((int64_t)s);
                     const aqg_i128 qq = vc == VC_U ? i128_from_u64(acc1[j]) : i128_from_i64((int64_t)acc1[j]);
-                    const aqg_i128 ss = mul_128_p1(sm, sm);
+                    const aqg_i128 ss = i128_mul(sm, sm);
                     const double sq = vc == VC_U ? u128_to_double(ss.hi, ss.lo) : i128_to_double(ss);
                     const double qdd = vc == VC_U ? u128_to_double(qq.hi, qq.lo) : i128_to_double(qq);
                     d = (qdd - sq / np1) / np1;
@@ -732,16 +719,16 @@ __global__ void __launch_bounds__(1024, 8) gid_agg_kernel(GidAgg a) {      // (e
             default: {
                 const bool mx = a.op == AQG_RED_MAX;
                 switch (a.vdt) {
-                case AQG_INT8: gid_store_minmax<int8_t>(a.out, gg, s, mx); break;
-                case AQG_INT16: gid_store_minmax<int16_t>(a.out, gg, s, mx); break;
-                case AQG_INT32: gid_store_minmax<int32_t>(a.out, gg, s, mx); break;
-                case AQG_INT64: gid_store_minmax<int64_t>(a.out, gg, s, mx); break;
-                case AQG_UINT8: case AQG_BOOL: gid_store_minmax<uint8_t>(a.out, gg, s, mx); break;
-                case AQG_UINT16: gid_store_minmax<uint16_t>(a.out, gg, s, mx); break;
-                case AQG_UINT32: gid_store_minmax<uint32_t>(a.out, gg, s, mx); break;
-                case AQG_UINT64: gid_store_minmax<uint64_t>(a.out, gg, s, mx); break;
-                case AQG_FLOAT: gid_store_minmax<float>(a.out, gg, s, mx); break;
-                default: gid_store_minmax<double>(a.out, gg, s, mx); break;
+                case AQG_INT8: store_minmax<int8_t>(a.out, gg, s, mx); break;
+                case AQG_INT16: store_minmax<int16_t>(a.out, gg, s, mx); break;
+                case AQG_INT32: store_minmax<int32_t>(a.out, gg, s, mx); break;
+                case AQG_INT64: store_minmax<int64_t>(a.out, gg, s, mx); break;
+                case AQG_UINT8: case AQG_BOOL: store_minmax<uint8_t>(a.out, gg, s, mx); break;
+                case AQG_UINT16: store_minmax<uint16_t>(a.out, gg, s, mx); break;
+                case AQG_UINT32: store_minmax<uint32_t>(a.out, gg, s, mx); break;
+                case AQG_UINT64: store_minmax<uint64_t>(a.out, gg, s, mx); break;
+                case AQG_FLOAT: store_minmax<float>(a.out, gg, s, mx); break;
+                default: store_minmax<double>(a.out, gg, s, mx); break;
                 }
             } break;
             }

@@ -495,26 +495,14 @@ __global__ void __launch_bounds__(256) counts64_kernel(const uint32_t* __restric
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
-int seg_realloc(aqg_ctx* ctx, uint32_t** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return AQG_OK;
-    if (*p) { aqg_pool_give(ctx, *p, *cap); *p = nullptr; *cap = 0; }
-    size_t want = need < 256 ? 256 : need;
-    if (void* q = aqg_pool_take(ctx, want, cap)) { *p = static_cast<uint32_t*>(q); return AQG_OK; }
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, want);
-    if (e != hipSuccess) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); (void)hipGetLastError(); return AQG_ERR_NOMEM; }
-    *p = static_cast<uint32_t*>(q);
-    *cap = want;
-    return AQG_OK;
-}
 size_t heads_bytes(uint32_t n) { return (((size_t)n + 32) / 32 + 8) * 4; }      // bit n included, two words of padding (the byte behind a block is read)
 
 // offsets + start bitmap of the flat layout, made once per build (uses the workspace: call before any sub-allocation of a call)
 int ensure_flat(aqg_ctx* ctx, aqg_groupby* g) {
     if (g->flat_valid) return AQG_OK;
     const uint32_t n = g->n, G = g->ngroups;
-    AQG_TRY(seg_realloc(ctx, &g->flat_off, &g->cap_flat_off, ((size_t)G + 2) * 4));
-    AQG_TRY(seg_realloc(ctx, &g->flat_heads, &g->cap_flat_heads, heads_bytes(n)));
+    AQG_TRY(aqg_dev_realloc(ctx, &g->flat_off, &g->cap_flat_off, ((size_t)G + 2) * 4));
+    AQG_TRY(aqg_dev_realloc(ctx, &g->flat_heads, &g->cap_flat_heads, heads_bytes(n)));
     AQG_TRY(aqg_ws_reset(ctx));
     AQG_TRY(aqg_ws_ensure(ctx, ((size_t)(G + 2048) / 2048 + 16) * 4 + 4096));
     uint32_t* bsum;
@@ -530,7 +518,7 @@ int ensure_flat(aqg_ctx* ctx, aqg_groupby* g) {
 }
 int ensure_short(aqg_ctx* ctx, aqg_groupby* g, uint32_t w) {
     if (g->flat_short_w == w && g->flat_short) return AQG_OK;
-    AQG_TRY(seg_realloc(ctx, &g->flat_short, &g->cap_flat_short, heads_bytes(g->n)));
+    AQG_TRY(aqg_dev_realloc(ctx, &g->flat_short, &g->cap_flat_short, heads_bytes(g->n)));
     AQG_HIP(ctx, hipMemsetAsync(g->flat_short, 0, heads_bytes(g->n), ctx->stream));
     hipLaunchKernelGGL(heads_kernel, dim3(aqg_grid(ctx, (uint64_t)g->ngroups + 1, 256, 1, 8)), dim3(256), 0, ctx->stream, g->flat_off, g->counts, g->ngroups,
                        (uint32_t*)nullptr, g->flat_short, w);
@@ -817,7 +805,7 @@ int aqg_grouped_reduce_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const v
     }
     // VAR / STDDEV: through the group-by plans, keyed by the group index of every flat position
     if (!g->flat_gid_valid) {
-        AQG_TRY(seg_realloc(ctx, &g->flat_gid, &g->cap_flat_gid, ((size_t)n + 4) * 4));
+        AQG_TRY(aqg_dev_realloc(ctx, &g->flat_gid, &g->cap_flat_gid, ((size_t)n + 4) * 4));
         AQG_TRY((seg_prefix<uint8_t, none_alg, SW_GID>(ctx, g, nullptr, n, g->flat_gid)));
         g->flat_gid_valid = true;
     }

@@ -3,11 +3,11 @@
 #include "tile_scatter.hpp"
 
 // ==== ordering a huge group table (G ~ N: h2o Q10) ========================================================================================
-// Group ids are ranks of first rows.  For <= 1e7 groups groupby.hip ranks through a bitmap over the rows and gathers the records in id
+// Group ids are ranks of first rows.  For <= 1e7 groups groupby_tail.hip ranks through a bitmap over the rows and gathers the records in id
 // order; at 1e9 groups those gathers fetch 600 GB.  Here the RECORDS are ordered instead, with the same tile scatter keyed on the first
 // row through an ORDER-PRESERVING bin f = umulhi(first_row, M), M = floor(P * 2^32 / rows): up to three levels of <= 64 bins leave P
 // partitions, partition p holding exactly the groups whose first rows fall into its row interval -- so its start is the id of its first
-// group -- and few enough of them that groupby.hip's sorted_emit_kernel ranks a partition inside LDS (bitmap of the interval) and
+// group -- and few enough of them that groupby_tail.hip's sorted_emit_kernel ranks a partition inside LDS (bitmap of the interval) and
 // emits the final columns from there.  (host side: aqg_sorted_tail below)
 
 // ---- ordering a huge group table: host ------------------------------------------------------------------------------------------------

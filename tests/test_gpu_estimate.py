@@ -1,5 +1,5 @@
 """GPU parity for calls WITHOUT a group-count hint over inputs large enough (>= 2^22 rows) that the library first estimates the count
-from a spread sample (estimate_groups / sample_distinct_kernel in csrc/groupby.hip) -- the only way the header layer ever calls
+from a spread sample (estimate_groups / sample_distinct_kernel in csrc/groupby_estimate.hip) -- the only way the header layer ever calls
 (include/aquery/hasher.h: max_groups_hint = 0).  Whatever the estimate says the result must be the oracle's: few groups, the all-ones
 key (the sample table's empty mark), wide tuples (counted by their hash), every row its own group, and keys clustered in runs (the
 case the clustering check exists for: a table sorted by its key)."""
