@@ -302,6 +302,9 @@ int aqg_reduce(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, void* out
                 d = (q - s * s / np1) / np1;
             } else if constexpr (std::is_unsigned_v<T>) {
                 unsigned __int128 s = as_u128(r.sum), q = as_u128(r.ssq);
+                // uint16: `a[i] * a[i]` is an int product that wraps negative from 46341 on, and the reference adds it SIGN-extended to its
+                // unsigned 128-bit sum (ssq += a[i] * a[i]).  The device's 64-bit sum of those products is exact as a signed value: extend it the same way.
+                if constexpr (sizeof(T) == 2) q = (unsigned __int128)(__int128)(int64_t)r.ssq.lo;
                 d = ((double)q - (double)(s * s) / np1) / np1;
             } else {
                 __int128 s = as_i128(r.sum), q = as_i128(r.ssq);

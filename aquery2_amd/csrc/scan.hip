@@ -36,7 +36,7 @@ template <class T, class ALG> __global__ void __launch_bounds__(SB) tile_reduce_
     if (threadIdx.x == 0) tile_agg[blockIdx.x] = total;
 }
 // K3: scan inside the tile with the carry-in; WRITER(out, i, inclusive_value)
-enum : int { W_SUMS = 0, W_AVGS = 1, W_MINS = 2, W_MAXS = 3, W_MAXP = 4 /* running max without the reference's seed (maxw, w >= n) */ };
+enum : int { W_SUMS = 0, W_AVGS = 1, W_MINS = 2, W_MAXS = 3, W_MAXP = 4, W_MINP = 5 /* W_MAXP / W_MINP: running max / min without the reference's seed (maxw / minw, w >= n) */ };
 
 // a scan that resumes a column sharded by row range (aqg_scan_resume): the sum of every earlier row in the result's LongType
 // and the number of earlier rows.  Kept apart from the tile accumulator, which is 64 bits wide for <= 4-byte integer columns
@@ -81,6 +81,7 @@ __device__ inline void write_tile(typename ALG::A run, const T (&v)[IT], uint32_
             if ((uint32_t)j < cnt) run = ALG::op(run, ALG::lift(v[j]));
             T r = run;
             if constexpr (WR == W_MAXS) { T seed = dlimits<T>::min(); r = seed > r ? seed : r; }  // maxs seeds with numeric_limits<T>::min()
+            if constexpr (WR == W_MINS) { T seed = dlimits<T>::max(); r = seed < r ? seed : r; }  // mins seeds with max(): +Inf rows come out as max()
             o[j] = r;
         }
         store_tile_striped(static_cast<T*>(out), tile_base, o, n, reinterpret_cast<T*>(stage_raw));
@@ -101,6 +102,9 @@ __global__ void __launch_bounds__(SB) tile_scan_kernel(const T* __restrict__ x, 
     for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) a = ALG::op(a, ALG::lift(v[j]));
     A total;
     A run = ALG::op(tile_prefix[blockIdx.x], block_scan_excl<ALG>(a, lds_w, total));
+    if constexpr (WR == W_AVGS && sizeof(T) == 8 && std::is_integral_v<T>) {
+        if (seed.row0 == 0) seed.i = i128_add(seed.i, first_row_rounding(x[0]));   // the column's own first row (a resumed shard's carry is the caller's)
+    }
     write_tile<T, ALG, WR>(run, v, cnt, base, blockIdx.x * TS, n, out, stage_raw, seed);
 }
 
@@ -672,7 +676,8 @@ int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& 
     // the look-back then costs 1.0 ms at 1e9 rows (the same kernel without any look-back: sums 3.35 ms, avgs 2.30 ms).
     // Packing that sum into one 62-bit word changed nothing (4.43 ms): at two workgroups per CU (the 16-byte results take the
     // registers) the look-back latency itself is exposed, not the number of words.
-    constexpr bool use_chain = WR == W_MINS || WR == W_MAXS || WR == W_MAXP;
+    constexpr bool use_chain = WR == W_MINS || WR == W_MAXS || WR == W_MAXP || WR == W_MINP;
+    constexpr bool is_min = WR == W_MINS || WR == W_MINP;
     if (!use_chain) {
         A *agg3, *chunk_tot;
         AQG_TRY(aqg_ws_get(ctx, ntiles, &agg3));
@@ -695,9 +700,8 @@ int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& 
     aqg_kernel_timer_begin(ctx);
     if constexpr (use_chain) {
         T none;                                              // the algebra's identity, spelled on the host
-        if constexpr (WR == W_MINS) none = dlimits<T>::max();
-        else if constexpr (std::is_floating_point_v<T>) none = -dlimits<T>::max();
-        else none = dlimits<T>::min();
+        if constexpr (std::is_floating_point_v<T>) none = is_min ? (T)INFINITY : -(T)INFINITY;
+        else none = is_min ? dlimits<T>::max() : dlimits<T>::min();
         hipLaunchKernelGGL((chained_scan_kernel<T, ALG, WR, M>), dim3(nlinks), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, ctrl, slots, out, mm_seed ? *mm_seed : none);
     }
     aqg_kernel_timer_end(ctx);
@@ -713,7 +717,7 @@ int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& 
     hipLaunchKernelGGL((agg_scan_kernel<ALG>), dim3(1), dim3(SB), 0, ctx->stream, agg, ntiles);
     hipLaunchKernelGGL((tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, agg, out, seed);
     if constexpr (use_chain) {
-        if (mm_seed) hipLaunchKernelGGL((apply_seed_kernel<T, WR != W_MINS>), dim3(aqg_grid(ctx, n, SB, 4, 8)), dim3(SB), 0, ctx->stream, static_cast<T*>(out), n, *mm_seed);
+        if (mm_seed) hipLaunchKernelGGL((apply_seed_kernel<T, !is_min>), dim3(aqg_grid(ctx, n, SB, 4, 8)), dim3(SB), 0, ctx->stream, static_cast<T*>(out), n, *mm_seed);
     }
     return aqg_check_launch(ctx, "prefix scan");
 }
@@ -767,7 +771,8 @@ int aqg_scan_minmax_seeded(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t
         if (seed_host) memcpy(&sd, seed_host, sizeof(T));
         const T* sp = seed_host ? &sd : nullptr;
         switch (op) {
-        case AQG_SCAN_MINS: case AQG_SCAN_MINW: return run_prefix<T, min_alg<T>, W_MINS>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
+        case AQG_SCAN_MINS: return run_prefix<T, min_alg<T>, W_MINS>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
+        case AQG_SCAN_MINW: return run_prefix<T, min_alg<T>, W_MINP>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
         case AQG_SCAN_MAXS: return run_prefix<T, max_alg<T>, W_MAXS>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
         case AQG_SCAN_MAXW: return run_prefix<T, max_alg<T>, W_MAXP>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
         }
@@ -881,7 +886,7 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
             const bool is_max = op == AQG_SCAN_MAXW;
             // the deque never expires anything when w == 0 or w >= n: plain running min / max (no seed)
             uint32_t ww = (w == 0 || w > n) ? n : w;
-            if (ww == n) return is_max ? run_prefix<T, max_alg<T>, W_MAXP>(ctx, x, n, out) : run_prefix<T, min_alg<T>, W_MINS>(ctx, x, n, out);
+            if (ww == n) return is_max ? run_prefix<T, max_alg<T>, W_MAXP>(ctx, x, n, out) : run_prefix<T, min_alg<T>, W_MINP>(ctx, x, n, out);
             // long windows: van Herk / Gil-Werman over C x 1024 LDS positions (C odd; two arrays of them; two workgroups per CU while
             // they take <= 78 KB and the kernel keeps to 64 VGPRs).  Needs a 16-byte aligned column; others take the doubling kernel.
             if (ww >= 128 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && n >= 64) {

@@ -68,16 +68,17 @@ template <class T> struct sum_alg {
         } else return (double)a;
     }
 };
+// Identities are the true ends of the ordering -- +-Inf for floating types, not +-max(): a fold that starts from max() turns a +Inf
+// row into max().  The reference's seeds (mins: max(), maxs / max: numeric_limits<T>::min()) are applied where a result is written.
 template <class T> struct min_alg {
     using A = T;
-    __device__ static A identity() { return dlimits<T>::max(); }
+    __device__ static A identity() { if constexpr (std::is_floating_point_v<T>) return (T)INFINITY; else return dlimits<T>::max(); }
     __device__ static A lift(T v) { return v; }
     __device__ static A op(A a, A b) { return b < a ? b : a; }
 };
 template <class T> struct max_alg {
     using A = T;
-    // true lowest value, not the reference's seed (the seed is applied when writing `maxs`)
-    __device__ static A identity() { if constexpr (std::is_floating_point_v<T>) return -dlimits<T>::max(); else return dlimits<T>::min(); }
+    __device__ static A identity() { if constexpr (std::is_floating_point_v<T>) return -(T)INFINITY; else return dlimits<T>::min(); }
     __device__ static A lift(T v) { return v; }
     __device__ static A op(A a, A b) { return b > a ? b : a; }
 };
@@ -127,6 +128,20 @@ template <class O> __device__ inline void store_tile_striped(O* __restrict__ out
     const uint32_t live = tile_base + TS <= n ? TS : n - tile_base;
 #pragma unroll
     for (int j = 0; j < IT; ++j) { uint32_t e = j * SB + t; if (e < live) out[tile_base + e] = lds[e]; }
+}
+// avgs (aggregations.h:219-228) starts its sum with `s = ret[0] = arr[0]`: the first element ROUNDED to double.  An 8-byte integer
+// beyond 2^53 does not survive that, and every later row divides the sum that carries the difference.  This is the difference
+// (LongType)(double)v - v as a 128-bit value (|difference| <= 2^10), to be added to the exact running sum.
+template <class T> __device__ inline aqg_i128 first_row_rounding(T v) {
+    static_assert(sizeof(T) == 8 && std::is_integral_v<T>, "narrower integers are exact in a double");
+    const double d = (double)v;
+    if constexpr (std::is_unsigned_v<T>) {
+        if (d >= 18446744073709551616.0) return i128_from_u64(0ull - (uint64_t)v);             // rounded up to 2^64
+        return i128_from_i64((int64_t)((uint64_t)d - (uint64_t)v));
+    } else {
+        if (d >= 9223372036854775808.0) return i128_from_u64(0x8000000000000000ull - (uint64_t)v);   // rounded up to 2^63
+        return i128_from_i64((int64_t)((uint64_t)(int64_t)d - (uint64_t)v));
+    }
 }
 template <class T> struct dsum_alg {
     using A = double;

@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(SB) seg_tile_reduce_kernel(const T* __restrict
     if (threadIdx.x == 0) tile_carry[blockIdx.x] = total;
 }
 
-enum : int { SW_SUMS = 0, SW_AVGS, SW_MINS, SW_MAXS, SW_MAXP, SW_VARS, SW_STDDEVS, SW_RAW, SW_MOM, SW_DIST, SW_GID, SW_RED_SUM, SW_RED_AVG, SW_RED_MIN, SW_RED_MAX, SW_RED_VAR, SW_RED_STDDEV };
+enum : int { SW_SUMS = 0, SW_AVGS, SW_MINS, SW_MAXS, SW_MAXP, SW_MINP, SW_VARS, SW_STDDEVS, SW_RAW, SW_MOM, SW_DIST, SW_GID, SW_RED_SUM, SW_RED_AVG, SW_RED_MIN, SW_RED_MAX, SW_RED_VAR, SW_RED_STDDEV };
 template <class T, int WR> struct seg_out {
     using type = std::conditional_t<WR == SW_SUMS || WR == SW_RED_SUM, std::conditional_t<std::is_floating_point_v<T>, double, aqg_i128>,
                  std::conditional_t<WR == SW_AVGS || WR == SW_VARS || WR == SW_STDDEVS || WR == SW_RED_AVG || WR == SW_RED_VAR || WR == SW_RED_STDDEV, double,
@@ -156,8 +156,12 @@ __global__ void __launch_bounds__(SB) seg_tile_scan_kernel(const T* __restrict__
         const double rows = (double)(p - s + 2);                        // rows of the group up to and including p (s = start + 1)
         if constexpr (WR == SW_SUMS || WR == SW_RED_SUM) {
             if constexpr (std::is_floating_point_v<T>) o[j] = run; else o[j] = sum_alg<T>::to_i128(run);
+        } else if constexpr (WR == SW_AVGS && sizeof(T) == 8 && std::is_integral_v<T>) {                            // avgs starts from the group's first row rounded to double
+            const A lead = (uint32_t)j < cnt ? first_row_rounding(x[s - 1]) : sum_alg<T>::identity();
+            o[j] = sum_alg<T>::to_double(sum_alg<T>::op(run, lead)) / rows;
         } else if constexpr (WR == SW_AVGS || WR == SW_RED_AVG) o[j] = sum_alg<T>::to_double(run) / rows;       // (s += arr[i]) / (double)(i + 1)
-        else if constexpr (WR == SW_MINS || WR == SW_MAXP || WR == SW_RED_MIN) o[j] = run;
+        else if constexpr (WR == SW_MAXP || WR == SW_MINP) o[j] = run;
+        else if constexpr (WR == SW_MINS || WR == SW_RED_MIN) { T seed = dlimits<T>::max(); o[j] = seed < run ? seed : run; }    // min / mins seed with max(): a +Inf group comes out as max()
         else if constexpr (WR == SW_MAXS || WR == SW_RED_MAX) { T seed = dlimits<T>::min(); o[j] = seed > run ? seed : run; }    // max / maxs seed with numeric_limits<T>::min() (D8)
         else if constexpr (WR == SW_VARS || WR == SW_STDDEVS) {                  // anchored moments of the group so far (mom_alg)
             const double var = var_from(run.s, run.q, (double)run.n);
@@ -263,8 +267,15 @@ __global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict_
     using ALG = sum_alg<T>;
     using A = typename ALG::A;
     using MX = max_alg<uint32_t>;
+    // Integer sums wrap, so one prefix over the whole extended tile serves every group.  A floating prefix does not: the difference of
+    // two prefixes carries the rounding of everything in front of the window, other groups' rows included (a group of ones behind a
+    // group of 1e30s came out as noise).  Floating columns restart the prefix at every group start (seg_alg).
+    constexpr bool SEG = std::is_floating_point_v<T>;
+    using SA = seg_alg<ALG>;
+    using C = typename SA::A;
     extern __shared__ __align__(16) unsigned char smem_raw[];
     __shared__ A lds_w[8];
+    __shared__ C lds_c[SEG ? 8 : 1];
     __shared__ uint32_t lds_m[8];
     const uint32_t tile_start = blockIdx.x * TS, tile_end = tile_start + TS < n ? tile_start + TS : n;
     const uint32_t H = (w - 1 + IT - 1) / IT * IT;                // LDS position p <-> row tile_start - H + p
@@ -272,6 +283,7 @@ __global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict_
     A* S = reinterpret_cast<A*>(smem_raw);
     uint32_t* LH = reinterpret_cast<uint32_t*>(S + L);            // per block of IT positions: {position + 1 of the last group start BEFORE the block (0: none in this tile), the block's start bits : 8}
     A carry = ALG::identity();
+    C carry_c = SA::identity();
     uint32_t carry_m = 0;
     for (uint32_t blk0 = 0; blk0 < nblk; blk0 += SB) {
         const uint32_t blk = blk0 + threadIdx.x;
@@ -289,18 +301,33 @@ __global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict_
         const uint32_t lh = hb ? blk * IT + (31 - __clz((int)hb)) + 1 : 0u;
         A loc[IT];
         A a = ALG::identity();
+        A excl;
+        if constexpr (SEG) {
+            C ac = SA::identity();
 #pragma unroll
-        for (int j = 0; j < IT; ++j) { a = ALG::op(a, ALG::lift(v[j])); loc[j] = a; }
-        A tot;
-        A excl = ALG::op(carry, block_scan_excl<ALG>(a, lds_w, tot));
+            for (int j = 0; j < IT; ++j) {
+                if ((hb >> j) & 1u) { ac.v = ALG::identity(); ac.s = 1; ++ac.c; }
+                ac.v = ALG::op(ac.v, ALG::lift(v[j]));
+                loc[j] = ac.v;
+            }
+            C totc;
+            const C ec = SA::op(carry_c, block_scan_excl<SA>(ac, lds_c, totc));
+            excl = ec.v;                                            // what the group that reaches into this block has summed before it
+            carry_c = SA::op(carry_c, totc);
+        } else {
+#pragma unroll
+            for (int j = 0; j < IT; ++j) { a = ALG::op(a, ALG::lift(v[j])); loc[j] = a; }
+            A tot;
+            excl = ALG::op(carry, block_scan_excl<ALG>(a, lds_w, tot));
+            carry = ALG::op(carry, tot);
+        }
         uint32_t totm;
         const uint32_t before = MX::op(carry_m, block_scan_excl<MX>(lh, lds_m, totm));
         if (blk < nblk) {
 #pragma unroll
-            for (int j = 0; j < IT; ++j) S[blk * IT + j] = ALG::op(excl, loc[j]);
+            for (int j = 0; j < IT; ++j) S[blk * IT + j] = (SEG && (hb & ((2u << j) - 1u))) ? loc[j] : ALG::op(excl, loc[j]);   // behind a start inside the block: no carry-in
             LH[blk] = (before << 8) | hb;
         }
-        carry = ALG::op(carry, tot);
         carry_m = MX::op(carry_m, totm);
     }
     __syncthreads();
@@ -312,6 +339,7 @@ __global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict_
         if (st && st - 1 > lower) lower = st - 1;
         const uint32_t len = idx - lower + 1;
         A s = lower ? ALG::sub(S[idx], S[lower - 1]) : S[idx];
+        if constexpr (SEG) { if (st && st - 1 == lower) s = S[idx]; }    // the window starts where the group does: the restarted prefix is the sum
         if constexpr (MODE == 0) {
             if constexpr (std::is_floating_point_v<T>) static_cast<double*>(out)[i] = s;
             else static_cast<aqg_i128*>(out)[i] = ALG::to_i128(s);
@@ -658,7 +686,7 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
         case AQG_SCAN_MINW: case AQG_SCAN_MAXW: {
             const bool is_max = op == AQG_SCAN_MAXW;
             // the deque never expires anything when w == 0 or w >= n: the running min / max of the group (no seed)
-            if (w == 0 || w >= n) return is_max ? seg_prefix<T, max_alg<T>, SW_MAXP>(ctx, g, x, n, out) : seg_prefix<T, min_alg<T>, SW_MINS>(ctx, g, x, n, out);
+            if (w == 0 || w >= n) return is_max ? seg_prefix<T, max_alg<T>, SW_MAXP>(ctx, g, x, n, out) : seg_prefix<T, min_alg<T>, SW_MINP>(ctx, g, x, n, out);
             const size_t ext = (size_t)TS + (w - 1 + 7) / 8 * 8;
             const size_t lds = ext * sizeof(T) * 2 + ext * 2 + 16;
             if (lds <= HALO_MAX_BYTES) {

@@ -236,7 +236,19 @@ int aqg_scan_sharded(aqg_comm* comm, int op, int t, const void* x, uint32_t n, u
     if (prefix_sum) {
         unsigned char carry[16] = {0};
         if (dt_is_fp(t)) { double s = -0.0; bool any = false; for (int r = 0; r < g.rank; ++r) if (g.rows(r)) { double a; memcpy(&a, g.moments(r), 8); s = any ? s + a : a; any = true; } memcpy(carry, &s, 8); }
-        else { unsigned __int128 s = 0; for (int r = 0; r < g.rank; ++r) if (g.rows(r)) s += (unsigned __int128)i128_of(g.moments(r)); memcpy(carry, &s, 16); }
+        else {
+            unsigned __int128 s = 0;
+            for (int r = 0; r < g.rank; ++r) if (g.rows(r)) s += (unsigned __int128)i128_of(g.moments(r));
+            // avgs of an 8-byte integer column sums from the COLUMN's first row rounded to double (`s = ret[0] = arr[0]`, aggregations.h:224;
+            // scan_dev.hpp first_row_rounding): the shards behind the one that holds that row add the rounding to their carry
+            if (op == AQG_SCAN_AVGS && esz == 8) for (int r = 0; r < g.rank; ++r) if (g.rows(r)) {
+                const uint64_t f = g.first_bits(r);
+                if (t == AQG_UINT64) s += (unsigned __int128)(double)f - (unsigned __int128)f;
+                else s += (unsigned __int128)((__int128)(double)(int64_t)f - (__int128)(int64_t)f);
+                break;
+            }
+            memcpy(carry, &s, 16);
+        }
         return aqg_scan_resume(ctx, op, t, x, n, before ? carry : nullptr, before, out);
     }
     if (prefix_mm || running_mm) {

@@ -138,7 +138,10 @@ int aqg_unary(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, uint32_t p
  * `out_host` receives 16 bytes: SUM -> GetLongType (int128/uint128/double),
  * MIN/MAX/FIRST/LAST -> T, COUNT -> uint64, AVG/VAR/STDDEV -> double.
  * Reference quirks kept on purpose: max seeds with numeric_limits<T>::min()
- * (:73, D8), var divides by len+1 (:347, D9).                                 */
+ * (:73, D8), var divides by len+1 (:347, D9).
+ * NaN rows: min / max, and sum / avg of floating columns, depend on the order of evaluation once a column holds a NaN (the
+ * reference's folds forget what came before it).  The call succeeds; the value is unspecified.  Of 0.0 and
+ * -0.0 either may come back as a min / max.  +-Inf rows are ordinary values.                                                  */
 typedef enum aqg_redop {
     AQG_RED_SUM = 0, AQG_RED_MIN = 1, AQG_RED_MAX = 2, AQG_RED_COUNT = 3, AQG_RED_AVG = 4,
     AQG_RED_VAR = 5, AQG_RED_STDDEV = 6, AQG_RED_FIRST = 7, AQG_RED_LAST = 8
@@ -155,7 +158,11 @@ int aqg_corr(aqg_ctx* ctx, int tx, const void* x, int ty, const void* y, uint32_
  * sumw/avgw/minw/maxw/ratiow :127-191,238-281 ; varw/stddevw :283-330 (D9: out-of-bounds read in the reference;
  *   here the population variance of the last min(w, i+1) rows, held to tests/test_gpu_variance.py)
  * deltas/prev/aggnext :439-485 ; ratios = ratiow(1) :193-201 ; vars/stddevs :350-381
- * window = elements [i-w+1, i]; growing prefix for i < w.                      */
+ * window = elements [i-w+1, i]; growing prefix for i < w.
+ * NaN rows: mins / maxs / minw / maxw, and sums / avgs / sumw / avgw of floating columns, are specified for every output row strictly
+ * before the column's first NaN row (sumw / avgw: before the reference's first NaN output, which an Inf row leaving the window causes
+ * too); behind it the values are unspecified and the call still succeeds.  Shifts and ratios move / divide NaNs like any value.
+ * avgs of an 8-byte integer column sums from its first row rounded to double, like the reference (`s = ret[0] = arr[0]`).     */
 typedef enum aqg_scanop {
     AQG_SCAN_SUMS = 0, AQG_SCAN_AVGS = 1, AQG_SCAN_MINS = 2, AQG_SCAN_MAXS = 3,
     AQG_SCAN_SUMW = 4, AQG_SCAN_AVGW = 5, AQG_SCAN_MINW = 6, AQG_SCAN_MAXW = 7,
