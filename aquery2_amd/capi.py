@@ -26,6 +26,15 @@ NP2TAG = {v: k for k, v in TAG2NP.items() if k != BOOL}
 NP2TAG[np.dtype(np.bool_)] = BOOL
 VEC_VEC, VEC_SCALAR, SCALAR_VEC = 0, 1, 2
 ORDER_ASC, ORDER_DESC, ORDER_NEG = 0, 1, 2
+SEL_LOWER, SEL_UPPER = 0, 1                                   # aqg_median: rank (c-1)/2 resp. c/2 of the c rows in ascending order
+ROUTE_SMALL, ROUTE_GROUP, ROUTE_SPLIT = 1, 2, 4               # aqg_select_last_routes
+# ctypes prototypes of the median entries (applied by load_library)
+MEDIAN_PROTOTYPES = {
+    "aqg_median": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_grouped_median": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_grouped_median_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_select_last_routes": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 PLAN_FAST_LDS, PLAN_SMALL_LDS, PLAN_BIG_LDS, PLAN_DENSE, PLAN_PART_ONE, PLAN_PART_TWO, PLAN_PART_ROUND1, PLAN_PART_WIDE, PLAN_SORTED_TAIL, PLAN_HBM_TABLE, PLAN_BUILD_PARTITIONED, PLAN_GID_PARTITION, PLAN_PACKED_VALUES, PLAN_RANGE_PARTITIONS, PLAN_ROW_EMIT, PLAN_PACKED_KEYS, PLAN_BUILD_LOOKUP = (1 << i for i in range(17))
 
 
@@ -60,6 +69,8 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
+        for f, argtypes in MEDIAN_PROTOTYPES.items():
+            getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
 
@@ -557,6 +568,28 @@ class Device:
         p = C.c_uint32()
         self._chk(self.lib.aqg_sort_last_passes(self.ctx, C.byref(p)), "aqg_sort_last_passes")
         return p.value
+
+    # -- median (a radix selection: include/aqg.h, median section)
+    def median(self, x, which=SEL_LOWER):
+        """the lower / upper median of a column, in the column's own dtype (0 for an empty column)"""
+        xd = self._dev(x)
+        buf = (C.c_ubyte * 16)()
+        self._chk(self.lib.aqg_median(self.ctx, which, xd.tag, xd.ptr, xd.n, buf), "aqg_median")
+        return np.frombuffer(bytes(buf), dtype=TAG2NP[xd.tag], count=1)[0]
+
+    def grouped_median(self, gb, x, which=SEL_LOWER, flat=False, keep=False, out=None):
+        """the median of every group of a build: `x` in row layout, or (flat=True) already in the flat layout"""
+        xd = self._dev(x)
+        out = out if out is not None else self.empty(gb.ngroups, TAG2NP[xd.tag])
+        fn = self.lib.aqg_grouped_median_flat if flat else self.lib.aqg_grouped_median
+        self._chk(fn(self.ctx, gb.h, which, xd.tag, xd.ptr, out.ptr), "aqg_grouped_median")
+        return out if keep else out.to_host()
+
+    def select_last_routes(self):
+        """(mask of ROUTE_* the groups of the last median call took, most digit passes any group needed)"""
+        r, p = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_select_last_routes(self.ctx, C.byref(r), C.byref(p)), "aqg_select_last_routes")
+        return r.value, p.value
 
     # -- group by
     def _keyargs(self, keys):

@@ -50,6 +50,7 @@ struct aqg_ctx {
     uint32_t sort_passes = 0;
     bool sort_passes_on_dev = false;
     uint32_t* sort_passes_dev = nullptr;
+    uint32_t* select_ctl = nullptr;              // aqg_median / aqg_grouped_median: control words of the last call (routes, passes, the flat call's result)
     // pinned host staging for small results
     void* host_stage = nullptr;
     size_t host_stage_cap = 0;
@@ -82,6 +83,7 @@ static inline uint32_t aqg_ceil_div(uint32_t n, uint32_t d) { return (uint32_t)(
 struct aqg_switch_set {
     uint32_t p1_max, sorted_tail_min;   // AQG_P1_MAX (1024), AQG_SORTED_TAIL_MIN (2^24)
     int p1_bins;                        // AQG_P1_BINS (0: planned)
+    uint32_t select_small_max, select_split_min;   // AQG_SELECT_SMALL_MAX (256), AQG_SELECT_SPLIT_MIN (2^20): the route thresholds of select.hip
     double pw_sigma;                    // AQG_PW_SIGMA (6)
     bool disable_p1, disable_p1_cursors, disable_ranged, disable_pw_defer, disable_build_partition, debug_flags, str_host;
 };

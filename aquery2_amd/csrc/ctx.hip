@@ -106,6 +106,7 @@ void aqg_ctx_destroy(aqg_ctx* ctx) {
     if (ctx->ws) hipFree(ctx->ws);
     if (ctx->rank_bm) hipFree(ctx->rank_bm);
     if (ctx->sort_passes_dev) hipFree(ctx->sort_passes_dev);
+    if (ctx->select_ctl) hipFree(ctx->select_ctl);
     for (auto& e : ctx->pool) hipFree(e.first);
     if (ctx->pool_big) hipFree(ctx->pool_big);
     if (ctx->host_stage) hipHostFree(ctx->host_stage);
@@ -411,8 +412,10 @@ int aqg_last_kernel_ms(aqg_ctx* ctx, float* ms) {
 const aqg_switch_set& aqg_switches() {
     auto num = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
     auto set = [](const char* name) { return getenv(name) != nullptr; };
+    auto unum = [](const char* name, uint32_t dflt) { return getenv(name) ? (uint32_t)strtoul(getenv(name), nullptr, 10) : dflt; };
     static const aqg_switch_set s{
         .p1_max = (uint32_t)num("AQG_P1_MAX", 1024), .sorted_tail_min = (uint32_t)num("AQG_SORTED_TAIL_MIN", 1 << 24), .p1_bins = num("AQG_P1_BINS", 0),
+        .select_small_max = unum("AQG_SELECT_SMALL_MAX", 256), .select_split_min = unum("AQG_SELECT_SPLIT_MIN", 1u << 20),
         .pw_sigma = getenv("AQG_PW_SIGMA") ? atof(getenv("AQG_PW_SIGMA")) : 6.0,
         .disable_p1 = set("AQG_DISABLE_P1"), .disable_p1_cursors = set("AQG_DISABLE_P1_CURSORS"), .disable_ranged = set("AQG_DISABLE_RANGED"),
         .disable_pw_defer = set("AQG_DISABLE_PW_DEFER"), .disable_build_partition = set("AQG_DISABLE_BUILD_PARTITION"),

@@ -1,0 +1,598 @@
+// select.hip -- aqg_median / aqg_grouped_median(_flat): the lower / upper median of a column and of every group's slice of the flat layout
+// (`median`, reference common/types.py:343; benchmark/h2o/groupby.sql:11-12, the one h2o query the reference leaves commented out).
+//
+// A selection, not a sort: rows are never moved.  Values are compared through their order-preserving images (key_image.hpp), and the
+// rank-k image of a slice is found by MSD radix selection: histogram one 8-bit digit of the rows that still match the bits chosen so far,
+// take the bin that holds the rank, subtract the rows below it, descend.  Every histogram pass also folds the AND and the OR of the
+// candidates' images: when they agree every candidate is the same value and the selection is over (one candidate is the plain case), and
+// when the chosen bin holds every candidate the next digit starts at their highest differing bit.
+// Group sizes of one call range from one row to the whole column, so there are three routes, chosen per group on the device:
+//   SMALL  up to AQG_SELECT_SMALL_MAX rows: a workgroup stages the images of a tile of flat positions (plus one group's worth behind it) in
+//          LDS and its wavefronts rank every group that STARTS in the tile by comparison counting, many groups per workgroup, one launch;
+//          groups of one or two rows take a lane each
+//   GROUP  one workgroup owns one group: an LDS histogram per digit, the slice re-read per digit (from L2 / Infinity Cache at h2o sizes)
+//   SPLIT  from AQG_SELECT_SPLIT_MIN rows: the group is cut into chunks, workgroups histogram a contiguous span of chunks in LDS and merge
+//          into the group's histogram in HBM; a small kernel chooses the bin between digits.  Digits are separated by launches: no
+//          workgroup ever waits for another.
+// A classify kernel over the offsets routes the groups (two compact lists, a per-tile first group); nothing comes back to the host, and
+// the number of launches depends on the dtype's width only.
+#include "aqg_internal.hpp"
+#include "dev_common.hpp"
+#include "groupby_handle.hpp"
+#include "key_image.hpp"
+
+namespace {
+
+constexpr int SB = 256;                       // lanes per workgroup
+constexpr int NWV = SB / 64;
+constexpr uint32_t TILE = 2048;               // SMALL: flat positions per workgroup
+constexpr uint32_t SMALL_CAP = 512;           // largest AQG_SELECT_SMALL_MAX (rows staged behind a tile)
+constexpr uint32_t SPLIT_CHUNK = 8192;        // SPLIT: rows per chunk
+constexpr int UNR = 4;                        // 16-byte loads in flight per lane
+enum { KIND_UNSIGNED = 0, KIND_SIGNED = 1, KIND_FP = 2 };
+enum { ROUTE_SMALL = 1, ROUTE_GROUP = 2, ROUTE_SPLIT = 4 };
+// control words of a call (device, owned by the context): read back by aqg_select_last_routes
+enum { CTL_ROUTES = 0, CTL_PASSES = 1, CTL_NGROUP = 2, CTL_NSPLIT = 3, CTL_NCHUNK = 4, CTL_RESULT = 8 /* 16 bytes */, CTL_OFF = 12 /* offsets {0, n} of the flat call */, CTL_WORDS = 16 };
+
+template <class U, int KIND> __device__ inline U image_of(U r) {
+    if constexpr (KIND == KIND_FP) return img_fp<U>(r);
+    else return img_int<U, KIND == KIND_SIGNED>(r);
+}
+template <class U, int KIND> __device__ inline U value_of(U i) {
+    if constexpr (KIND == KIND_FP) return unimg_fp<U>(i);
+    else return unimg_int<U, KIND == KIND_SIGNED>(i);
+}
+// images that several bit patterns share (both zeros, every NaN): the element is looked up in the slice instead of rebuilt
+template <class U, int KIND> __device__ inline bool image_is_shared(U i) {
+    if constexpr (KIND == KIND_FP) return i == img_fp_zero<U>() || i == img_fp_nan<U>();
+    else return false;
+}
+
+// the selection of one slice between digits
+struct SelState {
+    uint64_t prefix, kmask;       // image bits chosen so far / which bits those are
+    uint64_t vand, vor;           // AND / OR of the images of the last pass's candidates
+    uint32_t lo, hi, k, gidx;     // slice, rank among the candidates, group
+    uint32_t shift, done;         // low bit of the next digit; 1: the image is known, 2: known and shared (the element is looked up)
+    uint32_t cbase, passes;       // SPLIT: first chunk of the group; histogram passes so far
+};
+static_assert(sizeof(SelState) == 64, "SelState");
+
+// after a pass: the bin `bin` (rows below it: excl, rows in it: cnt, candidates: total) holds the rank.  true: st.prefix is the whole image.
+__device__ inline bool sel_advance(SelState& st, uint32_t bin, uint32_t excl, uint32_t cnt, uint32_t total) {
+    st.k -= excl;
+    st.prefix |= (uint64_t)bin << st.shift;
+    st.kmask |= 0xFFull << st.shift;
+    if (st.shift == 0) return true;
+    const uint64_t below = (1ull << st.shift) - 1;
+    if (cnt == total) {                                 // no candidate left the race: skip the bits they all share
+        const uint64_t diff = (st.vand ^ st.vor) & below;
+        if (!diff) { st.prefix |= st.vand & below; return true; }
+        const int hb = 63 - __clzll((long long)diff);
+        const uint32_t ns = hb >= 7 ? (uint32_t)hb - 7 : 0u;
+        const uint64_t mid = below & ~((1ull << (ns + 8)) - 1);
+        st.prefix |= st.vand & mid;
+        st.kmask |= mid;
+        st.shift = ns;
+    } else {
+        st.shift = st.shift >= 8 ? st.shift - 8 : 0u;
+    }
+    return false;
+}
+
+// histograms a pass fills.  2-byte columns count BOTH digits in their first pass: when every value shares the upper byte (small
+// counters, flags) the lower byte's counts are already there and the column is read once
+template <class U> constexpr uint32_t NHIST = sizeof(U) == 2 ? 2u : 1u;
+// the first pass of a 2-byte column found every row in one bin of the upper digit: the lower digit's histogram decides
+template <class U> __device__ inline bool both_digits_known(const SelState& st, uint32_t cnt, uint32_t total) {
+    return sizeof(U) == 2 && st.passes == 1 && cnt == total && ((st.vand ^ st.vor) >> 8) == 0;
+}
+
+struct OpAnd { template <class T> __device__ T operator()(T a, T b) const { return (T)(a & b); } };
+struct OpOr { template <class T> __device__ T operator()(T a, T b) const { return (T)(a | b); } };
+
+// inclusive sum over the SB lanes of a workgroup (wsum: NWV words of LDS)
+__device__ inline uint32_t block_scan_incl(uint32_t v, uint32_t* wsum) {
+    const int lane = lane_id(), wid = wave_id();
+    const uint32_t incl = wave_scan_incl(v, OpAdd{}, lane);
+    if (lane == 63) wsum[wid] = incl;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int w = 0; w < wid; ++w) base += wsum[w];
+    __syncthreads();
+    return base + incl;
+}
+
+// One histogram pass of a workgroup over rows [lo, hi) (lo < hi) of x: rows whose image matches `prefix` on `kmask` add their digit at
+// `shift` to h (LDS; NHIST * 256 bins) and fold into vand / vor.  16-byte loads over the aligned middle of the slice, UNR of them in flight per lane; the
+// up to 2 (V - 1) elements in front of and behind it take one lane each.
+template <class U, int KIND>
+__device__ inline void hist_rows(const U* __restrict__ x, uint32_t lo, uint32_t hi, U prefix, U kmask, uint32_t shift, uint32_t* h, U& vand, U& vor) {
+    constexpr uint32_t V = 16 / sizeof(U);
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(x + lo) & 15);
+    uint32_t hl = mis ? (16 - mis) / (uint32_t)sizeof(U) : 0u;
+    if (hl > hi - lo) hl = hi - lo;
+    const uint32_t a0 = lo + hl, nvec = (hi - a0) / V, ts = a0 + nvec * V, tl = hi - ts;
+    auto row = [&](U raw, bool live) {
+        const U im = image_of<U, KIND>(raw);
+        const bool m = live && ((U)(im ^ prefix) & kmask) == 0;
+        hist_add(h, (uint32_t)(im >> shift) & 255u, m);
+        if constexpr (NHIST<U> == 2) { if (kmask == 0) hist_add(h + 256, (uint32_t)im & 255u, m); }
+        vand &= m ? im : (U)~U(0);
+        vor |= m ? im : U(0);
+    };
+    {
+        const bool live = threadIdx.x < hl + tl;
+        const uint32_t e = threadIdx.x < hl ? lo + threadIdx.x : ts + (threadIdx.x - hl);
+        row(x[live ? e : lo], live);
+    }
+    const vec16<U>* xv = reinterpret_cast<const vec16<U>*>(x + a0);
+    for (uint32_t vb = 0; vb < nvec; vb += SB * UNR) {
+        vec16<U> r[UNR];
+        bool live[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const uint32_t vi = vb + u * SB + threadIdx.x;
+            live[u] = vi < nvec;
+            r[u] = xv[live[u] ? vi : nvec - 1];
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u)
+#pragma unroll
+            for (uint32_t e = 0; e < V; ++e) row(r[u].v[e], live[u]);
+    }
+}
+// vand / vor of the lanes -> the workgroup's (LDS)
+template <class U> __device__ inline void fold_and_or(U vand, U vor, unsigned long long* s_and, unsigned long long* s_or) {
+    vand = wave_reduce(vand, OpAnd{});
+    vor = wave_reduce(vor, OpOr{});
+    if (lane_id() == 0) { atomicAnd(s_and, (unsigned long long)vand); atomicOr(s_or, (unsigned long long)vor); }
+}
+// any element of rows [lo, hi) whose image is `im` -> *out (the writers race with equal-ranking elements: whichever lands is one of them)
+template <class U, int KIND> __device__ inline void find_rows(const U* __restrict__ x, uint32_t lo, uint32_t hi, U im, U* out) {
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += SB) {
+        const U raw = x[i];
+        if (image_of<U, KIND>(raw) == im) { *out = raw; break; }
+    }
+}
+
+struct BinSel { uint32_t bin, excl, cnt, total; };
+// the bin that holds rank k, from this lane's bin count c (lane = bin)
+__device__ inline void choose_bin(uint32_t c, uint32_t k, uint32_t* wsum, BinSel* sel) {
+    const uint32_t incl = block_scan_incl(c, wsum);
+    if (c && incl - c <= k && k < incl) { sel->bin = threadIdx.x; sel->excl = incl - c; sel->cnt = c; }
+    if (threadIdx.x == SB - 1) sel->total = incl;
+    __syncthreads();
+}
+
+// ---- routing: one lane per group ------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SB) select_classify_kernel(const uint32_t* __restrict__ off, uint32_t G, uint32_t small_max, uint32_t split_min, int which, int bits,
+                                                              uint32_t* __restrict__ tile_first, uint32_t* __restrict__ glist, SelState* __restrict__ sst, uint32_t* __restrict__ ctl) {
+    uint32_t mask = 0;
+    for (uint32_t g = blockIdx.x * SB + threadIdx.x; g < G; g += gridDim.x * SB) {
+        const uint32_t lo = off[g], hi = off[g + 1], c = hi - lo;
+        if (c == 0) continue;
+        if (c <= small_max) {
+            mask |= ROUTE_SMALL;
+            // the first SMALL group that starts in its tile: only a group whose predecessor starts in another tile, or is not SMALL, can be it
+            bool first = g == 0;
+            if (!first) { const uint32_t plo = off[g - 1], pc = lo - plo; first = plo / TILE != lo / TILE || pc > small_max || pc == 0; }
+            if (first) atomicMin(&tile_first[lo / TILE], g);
+        } else if (c < split_min) {
+            mask |= ROUTE_GROUP;
+            glist[atomicAdd(&ctl[CTL_NGROUP], 1u)] = g;
+        } else {
+            mask |= ROUTE_SPLIT;
+            SelState st{};
+            st.vand = ~0ull;
+            st.lo = lo; st.hi = hi; st.k = which ? c / 2 : (c - 1) / 2; st.gidx = g;
+            st.shift = (uint32_t)bits - 8;
+            sst[atomicAdd(&ctl[CTL_NSPLIT], 1u)] = st;
+        }
+    }
+    mask = wave_reduce(mask, OpOr{});
+    if (lane_id() == 0 && mask) {
+        atomicOr(&ctl[CTL_ROUTES], mask);
+        if (mask & ROUTE_SMALL) atomicMax(&ctl[CTL_PASSES], 1u);       // ranking by comparison: one pass over the group
+    }
+}
+// ---- SMALL ----------------------------------------------------------------------------------------------------------------------------------
+template <class U, int KIND>
+__global__ void __launch_bounds__(SB) select_small_kernel(const U* __restrict__ x, uint32_t n, const uint32_t* __restrict__ off, uint32_t G,
+                                                           const uint32_t* __restrict__ tile_first, uint32_t small_max, int which, U* __restrict__ out) {
+    constexpr uint32_t V = 16 / sizeof(U), ROWS = TILE + SMALL_CAP, PER = (ROWS / V + SB - 1) / SB;
+    __shared__ U img[ROWS];
+    __shared__ uint32_t goff[TILE + 2];
+    __shared__ uint32_t s_ng;
+    const uint32_t g0 = tile_first[blockIdx.x];
+    if (g0 == 0xFFFFFFFFu) return;
+    const uint32_t tbeg = blockIdx.x * TILE, tend = n - tbeg < TILE ? n : tbeg + TILE;
+    if (threadIdx.x == 0) s_ng = 0xFFFFFFFFu;
+    __syncthreads();
+    // offsets of the groups that start in this tile, and the end of the last one
+    for (uint32_t base = 0;; base += SB) {
+        const uint32_t i = base + threadIdx.x, gi = g0 + i < G ? g0 + i : G;
+        const uint32_t o = off[gi];
+        if (i < TILE + 2) goff[i] = o;
+        const bool beyond = o >= tend || gi == G;
+        if (beyond) atomicMin(&s_ng, i);
+        if (__syncthreads_or(beyond)) break;
+    }
+    const uint32_t ng = s_ng;
+    // one or two rows: a lane each, from the column itself
+    bool any = false;
+    for (uint32_t gi = threadIdx.x; gi < ng; gi += SB) {
+        const uint32_t lo = goff[gi], c = goff[gi + 1] - lo;
+        if (c > small_max || c == 0) continue;
+        if (c == 1) out[g0 + gi] = x[lo];
+        else if (c == 2) {
+            const U a = x[lo], b = x[lo + 1];
+            const bool swap = image_of<U, KIND>(b) < image_of<U, KIND>(a);
+            out[g0 + gi] = (swap != (which != 0)) ? b : a;
+        } else any = true;
+    }
+    if (!__syncthreads_or(any)) return;
+    // images of rows [tbeg, tbeg + ROWS) -> LDS
+    const uint32_t L = n - tbeg < ROWS ? n - tbeg : ROWS;
+    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && L >= V) {
+        const uint32_t nvec = L / V;
+        const vec16<U>* xv = reinterpret_cast<const vec16<U>*>(x + tbeg);
+        vec16<U> r[PER];
+#pragma unroll
+        for (uint32_t u = 0; u < PER; ++u) { const uint32_t vi = u * SB + threadIdx.x; r[u] = xv[vi < nvec ? vi : nvec - 1]; }
+#pragma unroll
+        for (uint32_t u = 0; u < PER; ++u) {
+            const uint32_t vi = u * SB + threadIdx.x;
+            if (vi < nvec) {
+#pragma unroll
+                for (uint32_t e = 0; e < V; ++e) img[vi * V + e] = image_of<U, KIND>(r[u].v[e]);
+            }
+        }
+        for (uint32_t i = nvec * V + threadIdx.x; i < L; i += SB) img[i] = image_of<U, KIND>(x[tbeg + i]);
+    } else {
+#pragma unroll 4
+        for (uint32_t i = threadIdx.x; i < L; i += SB) img[i] = image_of<U, KIND>(x[tbeg + i]);
+    }
+    __syncthreads();
+    // a wavefront per group: rank of every row = rows that sort before it (ties by position); the row of rank k is the answer
+    const uint32_t lane = lane_id();
+    for (uint32_t gi = wave_id(); gi < ng; gi += NWV) {
+        const uint32_t lo = goff[gi], c = goff[gi + 1] - lo;
+        if (c < 3 || c > small_max) continue;
+        const uint32_t base = lo - tbeg, k = which ? c / 2 : (c - 1) / 2;
+        for (uint32_t eb = 0; eb < c; eb += 64) {
+            const bool live = eb + lane < c;
+            const uint32_t ii = live ? eb + lane : c - 1;
+            const U mine = img[base + ii];
+            uint32_t less = 0;
+#pragma unroll 4
+            for (uint32_t j = 0; j < c; ++j) {
+                const U v = img[base + j];
+                less += (v < mine) | ((v == mine) & (j < ii));
+            }
+            if (live && less == k) out[g0 + gi] = x[lo + ii];
+        }
+    }
+}
+
+// ---- GROUP ----------------------------------------------------------------------------------------------------------------------------------
+template <class U, int KIND>
+__global__ void __launch_bounds__(SB) select_group_kernel(const U* __restrict__ x, const uint32_t* __restrict__ off, const uint32_t* __restrict__ glist,
+                                                           uint32_t* __restrict__ ctl, int which, U* __restrict__ out) {
+    __shared__ uint32_t h[256 * NHIST<U>];
+    __shared__ uint32_t wsum[NWV];
+    __shared__ unsigned long long s_and, s_or;
+    __shared__ BinSel sel;
+    const uint32_t ngl = ctl[CTL_NGROUP];
+    uint32_t maxp = 0;
+    for (uint32_t li = blockIdx.x; li < ngl; li += gridDim.x) {
+        const uint32_t g = glist[li], lo = off[g], hi = off[g + 1], c = hi - lo;
+        SelState st{};
+        st.k = which ? c / 2 : (c - 1) / 2;
+        st.shift = sizeof(U) * 8 - 8;
+        U result;
+        for (;;) {
+            __syncthreads();
+            for (uint32_t j = 0; j < NHIST<U>; ++j) h[j * 256 + threadIdx.x] = 0;
+            if (threadIdx.x == 0) { s_and = ~0ull; s_or = 0ull; }
+            __syncthreads();
+            U vand = (U)~U(0), vor = 0;
+            hist_rows<U, KIND>(x, lo, hi, (U)st.prefix, (U)st.kmask, st.shift, h, vand, vor);
+            fold_and_or(vand, vor, &s_and, &s_or);
+            __syncthreads();
+            ++st.passes;
+            st.vand = s_and; st.vor = s_or;
+            if (st.vand == st.vor) { result = (U)st.vand; break; }          // one candidate, or all of them equal
+            choose_bin(h[threadIdx.x], st.k, wsum, &sel);
+            if (both_digits_known<U>(st, sel.cnt, sel.total)) {
+                __syncthreads();
+                choose_bin(h[256 * (NHIST<U> - 1) + threadIdx.x], st.k, wsum, &sel);
+                result = (U)((st.vand & ~0xFFull) | sel.bin);
+                break;
+            }
+            if (sel_advance(st, sel.bin, sel.excl, sel.cnt, sel.total)) { result = (U)st.prefix; break; }
+        }
+        maxp = st.passes > maxp ? st.passes : maxp;
+        if (image_is_shared<U, KIND>(result)) find_rows<U, KIND>(x, lo, hi, result, out + g);
+        else if (threadIdx.x == 0) out[g] = value_of<U, KIND>(result);
+    }
+    if (threadIdx.x == 0 && maxp) atomicMax(&ctl[CTL_PASSES], maxp);
+}
+
+// ---- SPLIT ----------------------------------------------------------------------------------------------------------------------------------
+// chunk numbering: group s of the split list owns chunks [cbase, cbase + ceil(rows / SPLIT_CHUNK))
+__global__ void __launch_bounds__(SB) select_split_plan_kernel(SelState* __restrict__ sst, uint32_t* __restrict__ ctl) {
+    __shared__ uint32_t wsum[NWV];
+    const uint32_t ns = ctl[CTL_NSPLIT];
+    uint32_t carry = 0;
+    for (uint32_t b = 0; b < ns; b += SB) {
+        const uint32_t s = b + threadIdx.x;
+        const uint32_t nc = s < ns ? (sst[s].hi - sst[s].lo + SPLIT_CHUNK - 1) / SPLIT_CHUNK : 0u;
+        const uint32_t incl = block_scan_incl(nc, wsum);
+        if (s < ns) sst[s].cbase = carry + incl - nc;
+        __shared__ uint32_t tot;
+        if (threadIdx.x == SB - 1) tot = incl;
+        __syncthreads();
+        carry += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) ctl[CTL_NCHUNK] = carry;
+}
+// this workgroup's span of chunks and the split group its first chunk belongs to
+__device__ inline bool split_span(const SelState* sst, const uint32_t* ctl, uint32_t& q0, uint32_t& q1, uint32_t& s, uint32_t& ns) {
+    const uint32_t nchunk = ctl[CTL_NCHUNK];
+    ns = ctl[CTL_NSPLIT];
+    const uint32_t per = (nchunk + gridDim.x - 1) / gridDim.x;
+    const uint64_t b = (uint64_t)blockIdx.x * per;
+    if (b >= nchunk) return false;
+    q0 = (uint32_t)b;
+    q1 = b + per < nchunk ? (uint32_t)(b + per) : nchunk;
+    uint32_t l = 0, r = ns;                                 // the last s with cbase <= q0
+    while (r - l > 1) { const uint32_t m = (l + r) / 2; if (sst[m].cbase <= q0) l = m; else r = m; }
+    s = l;
+    return true;
+}
+template <class U, int KIND>
+__global__ void __launch_bounds__(SB) select_split_hist_kernel(const U* __restrict__ x, SelState* sst, const uint32_t* __restrict__ ctl, uint32_t* __restrict__ ghist) {
+    __shared__ uint32_t h[256 * NHIST<U>];
+    __shared__ unsigned long long s_and, s_or;
+    uint32_t q0, q1, s, ns;
+    if (!split_span(sst, ctl, q0, q1, s, ns)) return;
+    for (uint32_t j = 0; j < NHIST<U>; ++j) h[j * 256 + threadIdx.x] = 0;
+    if (threadIdx.x == 0) { s_and = ~0ull; s_or = 0ull; }
+    __syncthreads();
+    U vand = (U)~U(0), vor = 0;
+    bool touched = false;
+    auto flush = [&]() {                                    // this workgroup's share of group s -> HBM
+        if (touched) {
+            fold_and_or(vand, vor, &s_and, &s_or);
+            __syncthreads();
+            for (uint32_t j = 0; j < NHIST<U>; ++j)
+                if (h[j * 256 + threadIdx.x]) atomicAdd(&ghist[((size_t)s * NHIST<U> + j) * 256 + threadIdx.x], h[j * 256 + threadIdx.x]);
+            if (threadIdx.x == 0) { atomicAnd((unsigned long long*)&sst[s].vand, s_and); atomicOr((unsigned long long*)&sst[s].vor, s_or); }
+            __syncthreads();
+            for (uint32_t j = 0; j < NHIST<U>; ++j) h[j * 256 + threadIdx.x] = 0;
+            if (threadIdx.x == 0) { s_and = ~0ull; s_or = 0ull; }
+            __syncthreads();
+        }
+        vand = (U)~U(0); vor = 0; touched = false;
+    };
+    for (uint32_t q = q0; q < q1; ++q) {
+        while (s + 1 < ns && sst[s + 1].cbase <= q) { flush(); ++s; }
+        if (sst[s].done) continue;
+        const uint32_t lo = sst[s].lo + (q - sst[s].cbase) * SPLIT_CHUNK, ghi = sst[s].hi;
+        const uint32_t hi = ghi - lo < SPLIT_CHUNK ? ghi : lo + SPLIT_CHUNK;
+        hist_rows<U, KIND>(x, lo, hi, (U)sst[s].prefix, (U)sst[s].kmask, sst[s].shift, h, vand, vor);
+        touched = true;
+    }
+    flush();
+}
+template <class U, int KIND>
+__global__ void __launch_bounds__(SB) select_split_choose_kernel(SelState* __restrict__ sst, uint32_t* __restrict__ ctl, uint32_t* __restrict__ ghist, U* __restrict__ out) {
+    __shared__ uint32_t wsum[NWV];
+    __shared__ BinSel sel;
+    const uint32_t ns = ctl[CTL_NSPLIT];
+    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x) {
+        SelState st = sst[s];
+        __syncthreads();                                    // (every lane has read the state before lane 0 rewrites it)
+        if (st.done) continue;
+        uint32_t* gh = ghist + (size_t)s * NHIST<U> * 256;
+        const uint32_t c = gh[threadIdx.x], c2 = gh[256 * (NHIST<U> - 1) + threadIdx.x];
+        for (uint32_t j = 0; j < NHIST<U>; ++j) gh[j * 256 + threadIdx.x] = 0;
+        ++st.passes;
+        bool done;
+        if (st.vand == st.vor) { st.prefix = st.vand; done = true; }
+        else {
+            choose_bin(c, st.k, wsum, &sel);
+            if (both_digits_known<U>(st, sel.cnt, sel.total)) {
+                __syncthreads();
+                choose_bin(c2, st.k, wsum, &sel);
+                st.prefix = (st.vand & ~0xFFull) | sel.bin;
+                done = true;
+            } else done = sel_advance(st, sel.bin, sel.excl, sel.cnt, sel.total);
+        }
+        if (threadIdx.x == 0) {
+            if (done) {
+                const U result = (U)st.prefix;
+                st.done = image_is_shared<U, KIND>(result) ? 2u : 1u;
+                if (st.done == 1) out[st.gidx] = value_of<U, KIND>(result);
+                atomicMax(&ctl[CTL_PASSES], st.passes);
+            }
+            st.vand = ~0ull; st.vor = 0ull;
+            sst[s] = st;
+        }
+    }
+}
+// groups whose image is shared by several bit patterns: any element of the slice with that image
+template <class U, int KIND>
+__global__ void __launch_bounds__(SB) select_split_find_kernel(const U* __restrict__ x, const SelState* __restrict__ sst, const uint32_t* __restrict__ ctl, U* __restrict__ out) {
+    uint32_t q0, q1, s, ns;
+    if (!split_span(sst, ctl, q0, q1, s, ns)) return;
+    for (uint32_t q = q0; q < q1; ++q) {
+        while (s + 1 < ns && sst[s + 1].cbase <= q) ++s;
+        if (sst[s].done != 2) continue;
+        const uint32_t lo = sst[s].lo + (q - sst[s].cbase) * SPLIT_CHUNK, ghi = sst[s].hi;
+        find_rows<U, KIND>(x, lo, ghi - lo < SPLIT_CHUNK ? ghi : lo + SPLIT_CHUNK, (U)sst[s].prefix, out + sst[s].gidx);
+    }
+}
+
+__global__ void select_flat_offsets_kernel(uint32_t* off, uint32_t n) { off[0] = 0; off[1] = n; }
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------------------
+struct SelSwitches { uint32_t small_max, split_min; };
+
+uint32_t split_cap(uint32_t n, uint32_t G, uint32_t split_min) {       // most groups the SPLIT route can meet
+    const uint32_t by_rows = n / (split_min ? split_min : 1u);
+    return (by_rows < G ? by_rows : G) + 1;
+}
+size_t select_ws_bytes(uint32_t n, uint32_t G, SelSwitches sw) {
+    auto rup = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const uint32_t glcap = (n / (sw.small_max + 1) < G ? n / (sw.small_max + 1) : G) + 1;
+    return rup(((size_t)aqg_ceil_div(n, TILE) + 1) * 4) + rup((size_t)glcap * 4) + rup((size_t)split_cap(n, G, sw.split_min) * (sizeof(SelState) + 2048)) + 4096;
+}
+int ensure_ctl(aqg_ctx* ctx) {
+    if (!ctx->select_ctl) AQG_HIP(ctx, hipMalloc(&ctx->select_ctl, 256));
+    AQG_HIP(ctx, hipMemsetAsync(ctx->select_ctl, 0, CTL_WORDS * 4, ctx->stream));
+    return AQG_OK;
+}
+// the three routes over a column in the flat layout (workspace sized by select_ws_bytes and not reset in here; the control words are zero)
+template <class U, int KIND>
+int run_select(aqg_ctx* ctx, int which, const void* xv, uint32_t n, const uint32_t* off, uint32_t G, SelSwitches sw, void* outv) {
+    const U* x = static_cast<const U*>(xv);
+    U* out = static_cast<U*>(outv);
+    uint32_t* ctl = ctx->select_ctl;
+    const uint32_t ntiles = aqg_ceil_div(n, TILE), scap = split_cap(n, G, sw.split_min);
+    const uint32_t glcap = (n / (sw.small_max + 1) < G ? n / (sw.small_max + 1) : G) + 1;
+    // routes no group of this call can take are not launched (what the host knows without a look at the groups: n bounds every group)
+    const bool do_small = sw.small_max >= 1, do_group = n > sw.small_max && sw.split_min > sw.small_max + 1, do_split = n >= sw.split_min && n > sw.small_max;
+    uint32_t *tile_first, *glist, *ghist;
+    SelState* sst;
+    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles + 1, &tile_first));
+    AQG_TRY(aqg_ws_get(ctx, glcap, &glist));
+    AQG_TRY(aqg_ws_get(ctx, scap, &sst));
+    AQG_TRY(aqg_ws_get(ctx, (size_t)scap * 256 * NHIST<U>, &ghist));
+    if (do_small) AQG_HIP(ctx, hipMemsetAsync(tile_first, 0xFF, (size_t)ntiles * 4, ctx->stream));
+    if (do_split) AQG_HIP(ctx, hipMemsetAsync(ghist, 0, (size_t)scap * 1024 * NHIST<U>, ctx->stream));
+    const unsigned ggrid = aqg_grid(ctx, G, SB, 1, 8);
+    hipLaunchKernelGGL(select_classify_kernel, dim3(ggrid), dim3(SB), 0, ctx->stream, off, G, sw.small_max, sw.split_min, which, (int)sizeof(U) * 8, tile_first, glist, sst, ctl);
+    aqg_kernel_timer_begin(ctx);
+    if (do_small) {
+        hipLaunchKernelGGL((select_small_kernel<U, KIND>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, off, G, tile_first, sw.small_max, which, out);
+    }
+    if (do_group) {
+        const uint32_t cap = (uint32_t)ctx->num_cu * 8;
+        hipLaunchKernelGGL((select_group_kernel<U, KIND>), dim3(glcap < cap ? glcap : cap), dim3(SB), 0, ctx->stream, x, off, glist, ctl, which, out);
+    }
+    if (do_split) {
+        const uint64_t chunks = (uint64_t)aqg_ceil_div(n, SPLIT_CHUNK) + scap;
+        const unsigned hgrid = (unsigned)(chunks < (uint64_t)ctx->num_cu * 8 ? chunks : (uint64_t)ctx->num_cu * 8);
+        const unsigned cgrid = scap < 1024u ? scap : 1024u;
+        hipLaunchKernelGGL(select_split_plan_kernel, dim3(1), dim3(SB), 0, ctx->stream, sst, ctl);
+        for (size_t p = 0; p < sizeof(U); ++p) {
+            hipLaunchKernelGGL((select_split_hist_kernel<U, KIND>), dim3(hgrid), dim3(SB), 0, ctx->stream, x, sst, ctl, ghist);
+            hipLaunchKernelGGL((select_split_choose_kernel<U, KIND>), dim3(cgrid), dim3(SB), 0, ctx->stream, sst, ctl, ghist, out);
+        }
+        if constexpr (KIND == KIND_FP) hipLaunchKernelGGL((select_split_find_kernel<U, KIND>), dim3(hgrid), dim3(SB), 0, ctx->stream, x, sst, ctl, out);
+    }
+    aqg_kernel_timer_end(ctx);
+    return aqg_check_launch(ctx, "median selection");
+}
+int dispatch_select(aqg_ctx* ctx, int which, int t, const void* x, uint32_t n, const uint32_t* off, uint32_t G, SelSwitches sw, void* out) {
+    switch (t) {
+    case AQG_UINT8: case AQG_BOOL: return run_select<uint8_t, KIND_UNSIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_UINT16: return run_select<uint16_t, KIND_UNSIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_UINT32: return run_select<uint32_t, KIND_UNSIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_UINT64: return run_select<uint64_t, KIND_UNSIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_INT8: return run_select<uint8_t, KIND_SIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_INT16: return run_select<uint16_t, KIND_SIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_INT32: return run_select<uint32_t, KIND_SIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_INT64: return run_select<uint64_t, KIND_SIGNED>(ctx, which, x, n, off, G, sw, out);
+    case AQG_FLOAT: return run_select<uint32_t, KIND_FP>(ctx, which, x, n, off, G, sw, out);
+    case AQG_DOUBLE: return run_select<uint64_t, KIND_FP>(ctx, which, x, n, off, G, sw, out);
+    }
+    return AQG_ERR_DTYPE;
+}
+int select_esz(int t) {
+    switch (t) {
+    case AQG_INT8: case AQG_UINT8: case AQG_BOOL: return 1;
+    case AQG_INT16: case AQG_UINT16: return 2;
+    case AQG_INT32: case AQG_UINT32: case AQG_FLOAT: return 4;
+    case AQG_INT64: case AQG_UINT64: case AQG_DOUBLE: return 8;
+    }
+    return 0;
+}
+SelSwitches select_switches() {
+    const aqg_switch_set& s = aqg_switches();
+    return SelSwitches{s.select_small_max < SMALL_CAP ? s.select_small_max : SMALL_CAP, s.select_split_min};
+}
+int check_grouped(aqg_ctx* ctx, const aqg_groupby* g, int which, int t, const void* x, const void* out) {
+    if (!ctx || !g) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: bad argument");
+    if (!g->has_reversemap || !g->has_counts) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: the handle was not made by aqg_groupby_build");
+    if (which != AQG_SEL_LOWER && which != AQG_SEL_UPPER) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: which must be AQG_SEL_LOWER or AQG_SEL_UPPER");
+    if (!select_esz(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "grouped median: 1-, 2-, 4- and 8-byte numeric columns and BOOL");
+    if ((!x || !out) && g->n) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: null column");
+    return AQG_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int aqg_median(aqg_ctx* ctx, int which, int t, const void* x, uint32_t n, void* out_host16) {
+    if (!ctx || !out_host16) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_median: bad argument");
+    if (which != AQG_SEL_LOWER && which != AQG_SEL_UPPER) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_median: which must be AQG_SEL_LOWER or AQG_SEL_UPPER");
+    if (!select_esz(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_median: 1-, 2-, 4- and 8-byte numeric columns and BOOL");
+    if (!x && n) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_median: null column");
+    AQG_CHECK_ROWS(ctx, n, "aqg_median");
+    AQG_TRY(ensure_ctl(ctx));
+    memset(out_host16, 0, 16);
+    if (n == 0) return AQG_OK;
+    const SelSwitches sw = select_switches();
+    AQG_TRY(aqg_ws_reset(ctx));
+    AQG_TRY(aqg_ws_ensure(ctx, select_ws_bytes(n, 1, sw)));
+    uint32_t* ctl = ctx->select_ctl;
+    hipLaunchKernelGGL(select_flat_offsets_kernel, dim3(1), dim3(1), 0, ctx->stream, ctl + CTL_OFF, n);
+    AQG_TRY(dispatch_select(ctx, which, t, x, n, ctl + CTL_OFF, 1, sw, ctl + CTL_RESULT));
+    return aqg_d2h(ctx, out_host16, ctl + CTL_RESULT, 16);
+}
+
+int aqg_grouped_median_flat(aqg_ctx* ctx, aqg_groupby* g, int which, int t, const void* xflat, void* out_dev) {
+    AQG_TRY(check_grouped(ctx, g, which, t, xflat, out_dev));
+    AQG_TRY(ensure_ctl(ctx));
+    const uint32_t n = g->n, G = g->ngroups;
+    if (n == 0 || G == 0) return AQG_OK;
+    const uint32_t* off = aqg_groupby_offsets(g);
+    if (!off) return AQG_ERR_HIP;
+    const SelSwitches sw = select_switches();
+    AQG_TRY(aqg_ws_reset(ctx));
+    AQG_TRY(aqg_ws_ensure(ctx, select_ws_bytes(n, G, sw)));
+    return dispatch_select(ctx, which, t, xflat, n, off, G, sw, out_dev);
+}
+
+int aqg_grouped_median(aqg_ctx* ctx, aqg_groupby* g, int which, int t, const void* x, void* out_dev) {
+    AQG_TRY(check_grouped(ctx, g, which, t, x, out_dev));
+    AQG_TRY(ensure_ctl(ctx));
+    const uint32_t n = g->n, G = g->ngroups;
+    if (n == 0 || G == 0) return AQG_OK;
+    const uint32_t* off = aqg_groupby_offsets(g);
+    if (!off) return AQG_ERR_HIP;
+    const SelSwitches sw = select_switches();
+    const int esz = select_esz(t);
+    AQG_TRY(aqg_ws_reset(ctx));
+    AQG_TRY(aqg_ws_ensure(ctx, (size_t)n * esz + 4096 + aqg_postproc_ws_bytes(n, G, esz) + select_ws_bytes(n, G, sw)));
+    unsigned char* xs;
+    AQG_TRY(aqg_ws_get(ctx, (size_t)n * esz + 64, &xs));
+    AQG_TRY(aqg_radix_by_group(ctx, g, nullptr, x, esz, xs, /*ws_managed=*/true));
+    return dispatch_select(ctx, which, t, xs, n, off, G, sw, out_dev);
+}
+
+int aqg_select_last_routes(aqg_ctx* ctx, uint32_t* routes_host, uint32_t* passes_host) {
+    if (!ctx || !routes_host || !passes_host) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_select_last_routes: bad argument");
+    uint32_t w[2] = {0, 0};
+    if (ctx->select_ctl) AQG_TRY(aqg_d2h(ctx, w, ctx->select_ctl, 8));
+    *routes_host = w[0];
+    *passes_host = w[1];
+    return AQG_OK;
+}
+
+} // extern "C"

@@ -1,6 +1,6 @@
 // sort.hip -- aqg_sort_rows: a stable multi-column sort of row ids (TableInfo::order_by, reference server/table.h:447-465).
 //
-// Keys are mapped to order-preserving unsigned images (sign flip for signed types, the sign-dependent flip for floats after
+// Keys are mapped to order-preserving unsigned images (key_image.hpp: sign flip for signed types, the sign-dependent flip for floats after
 // canonicalising -0.0 and NaN, complement for DESC, two's-complement negation for NEG) and packed, least significant key at the
 // bottom, into segments of at most 64 bits; a 16-byte key is two segments.  The segments are sorted one after the other, least
 // significant first, by an LSD radix sort over 8-bit digits:
@@ -18,6 +18,7 @@
 // Up to SMALL rows are sorted by one workgroup in registers and LDS, every segment and pass in one launch.
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
+#include "key_image.hpp"
 
 namespace {
 
@@ -35,23 +36,6 @@ struct SortField { const void* ptr; uint8_t dt, ord, part, shift; };   // part: 
 struct SortSeg { SortField f[8]; int nf; int bits; };
 struct SortSegs { SortSeg s[MAX_SEGS]; int nseg; };
 
-template <class U, bool SIGNED> __device__ inline uint64_t enc_int(const void* p, uint32_t row, int ord) {
-    U r = static_cast<const U*>(p)[row];
-    if (ord == AQG_ORDER_NEG) r = (U)(U(0) - r);
-    if constexpr (SIGNED) r = (U)(r ^ (U(1) << (sizeof(U) * 8 - 1)));
-    if (ord == AQG_ORDER_DESC) r = (U)~r;
-    return (uint64_t)r;
-}
-template <class U, class B> __device__ inline uint64_t enc_fp(const void* p, uint32_t row, int ord) {
-    constexpr B sign = B(1) << (sizeof(B) * 8 - 1), expo = sizeof(B) == 4 ? (B)0x7f800000u : (B)0x7ff0000000000000ull;
-    constexpr B qnan = sizeof(B) == 4 ? (B)0x7fc00000u : (B)0x7ff8000000000000ull;
-    B b = static_cast<const B*>(p)[row];
-    if ((b & ~sign) == 0) b = 0;                       // -0.0 == +0.0
-    else if ((b & ~sign) > expo) b = qnan;             // every NaN is one key, after +inf
-    b = (b & sign) ? (B)~b : (B)(b | sign);
-    if (ord == AQG_ORDER_DESC) b = (B)~b;
-    return (uint64_t)b;
-}
 __device__ inline uint64_t enc_128(const void* p, uint32_t row, int ord, bool sgn, int part) {
     const uint64_t* q = static_cast<const uint64_t*>(p) + 2 * (size_t)row;
     uint64_t lo = q[0], hi = q[1];
@@ -82,19 +66,6 @@ __device__ inline uint64_t encode(const SortSeg& s, uint32_t row) {
     uint64_t img = 0;
     for (int i = 0; i < s.nf; ++i) img |= enc_field(s.f[i], row);
     return img;
-}
-
-// LDS histogram add of one digit per lane: a wavefront whose live lanes share the digit adds once (constant and near-constant
-// digit positions would otherwise serialise 64 lanes on one bank)
-__device__ inline void hist_add(uint32_t* h, uint32_t d, bool live) {
-    const uint64_t act = __ballot(live);
-    const uint32_t first = __shfl(d, act ? __ffsll((long long)act) - 1 : 0, 64);
-    const uint64_t same = __ballot(live && d == first);
-    if (same == act) {
-        if (act && lane_id() == __ffsll((long long)act) - 1) atomicAdd(&h[first], (uint32_t)__popcll(act));
-    } else if (live) {
-        atomicAdd(&h[d], 1u);
-    }
 }
 
 // Tile-local stable positions of ROUNDS x RB rows by digit: pos = (rows of smaller digits) + (rows of the same digit in earlier

@@ -203,6 +203,35 @@ int aqg_sort_rows(aqg_ctx* ctx, int nkeys, const int* key_dtypes, const void* co
 /* digit passes the last aqg_sort_rows on this context actually ran (skipped passes not counted) */
 int aqg_sort_last_passes(aqg_ctx* ctx, uint32_t* passes_host);
 
+/* ---- median ------------------------------------------------------------------
+ * `median`, a built-in aggregate of the query language (common/types.py:343: fnmedian, result type "as is"); the reference's
+ * server/aggregations.h has no body for it and its h2o file leaves the query commented out (benchmark/h2o/groupby.sql:11-12:
+ * `median(v3), stddev(v3) ... GROUP BY id4, id5`).  A device radix SELECTION over order-preserving images, not a sort.
+ * Result: the column's own dtype `t`, an ELEMENT OF THE INPUT bit for bit -- the row of rank (c-1)/2 (AQG_SEL_LOWER) or c/2
+ * (AQG_SEL_UPPER), integer division, of the c rows in ascending order.  AQG_SEL_LOWER is what `median` means here: an odd count gives
+ * the middle element, an even count the lower of the two middle ones (meant to match a SQL engine's "element, rounded down" median;
+ * PARITY UNPINNED: no executable reference median exists).  AQG_SEL_UPPER lets a caller form h2o's averaged
+ * median as (lower + upper) / 2 with aqg_ewise.
+ * Order: that of aqg_sort_rows under AQG_ORDER_ASC.  Integers and BOOL by value.  Floating columns: -0.0 and +0.0 are one value
+ * (which zero comes back is unspecified when the slice holds both); every NaN is one value above +inf, and when the rank falls
+ * among the NaNs the result is a NaN of unspecified sign and payload -- the call succeeds.
+ * Dtypes: INT8/16/32/64, UINT8/16/32/64, BOOL, FLOAT, DOUBLE; anything else (the 128-bit integers too: the flat layout does not
+ * carry 16-byte elements) returns AQG_ERR_DTYPE with nothing written.
+ *   aqg_median               the whole column; sizeof(T) bytes at the start of 16 zeroed HOST bytes.  n == 0: AQG_OK and 16 zero bytes.
+ *   aqg_grouped_median       out_dev[g] for all G groups in group order, x in ROW layout (brought into the flat layout in workspace)
+ *   aqg_grouped_median_flat  the same over a column already in the FLAT LAYOUT of the build (see the per-group scans below)
+ * The grouped forms need a handle of aqg_groupby_build (as aqg_grouped_scan); G == 0 returns AQG_OK.  The input is never modified.
+ * Asynchronous on the context's stream (aqg_median synchronises for its host result: the call's one round trip), scratch from
+ * the context workspace, no allocation in steady state, and a number of launches that does not depend on the group count.
+ * aqg_select_last_routes (diagnostic, like aqg_sort_last_passes): a mask of the routes the groups of the last call took
+ * (1 SMALL, 2 GROUP, 4 SPLIT) and the largest number of digit passes any group needed.               */
+enum { AQG_SEL_LOWER = 0, AQG_SEL_UPPER = 1 };
+int aqg_median(aqg_ctx* ctx, int which, int t, const void* x, uint32_t n, void* out_host16);
+struct aqg_groupby;
+int aqg_grouped_median(aqg_ctx* ctx, struct aqg_groupby* g, int which, int t, const void* x, void* out_dev);
+int aqg_grouped_median_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, int t, const void* xflat, void* out_dev);
+int aqg_select_last_routes(aqg_ctx* ctx, uint32_t* routes_host, uint32_t* passes_host);
+
 /* ---- hash group-by -----------------------------------------------------------
  * Replaces AQHashTable (server/hasher.h:146-199) + set::hashtable_push
  * (server/unordered_dense.h:1117-1147) + HashTableFactory::get (:327-357).

@@ -82,6 +82,22 @@ T first(const VT<T>& v) { return v.size ? aq::device_reduce<T>(AQG_RED_FIRST, v)
 template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
 T last(const VT<T>& v) { return v.size ? aq::device_reduce<T>(AQG_RED_LAST, v) : T(0); }
 
+// median (common/types.py:343: fnmedian, result type "as is"; benchmark/h2o/groupby.sql:11-12): the LOWER median, an element of the
+// input (include/aqg.h, median section); the reference's header declares no body for it.  Empty input: T(0), like first / last.
+template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+T median(const VT<T>& v) {
+    if (!v.size) return T(0);
+    auto& rt = aq::dev::Runtime::get();
+    alignas(16) unsigned char buf[16];
+    if (!rt.deferred_reduce(v.container, aq::dev::Runtime::DEFERRED_MEDIAN, buf)) {      // not a deferred `col[vecs[g]]`: this very vector
+        aq::dev::In in(v.container, (size_t)v.size * sizeof(T), v.capacity == 0);
+        aq::dev::check(aqg_median(rt.ctx(), AQG_SEL_LOWER, aq::dev::tag_of<T>::value, in.d, v.size, buf), "aqg_median");
+    }
+    T r;
+    std::memcpy(&r, buf, sizeof(T));
+    return r;
+}
+
 template <class T, template <typename...> class VT, class T2, template <typename...> class VT2,
           std::enable_if_t<aq::is_vt<VT, T> && aq::is_vt<VT2, T2>>* = nullptr>
 double corr(const VT<T>& x, const VT2<T2>& y) {
@@ -166,7 +182,7 @@ template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constex
 #define AQ_SCALAR_ZERO(name) template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T name(const T&) { return 0; }
 #define AQ_SCALAR_WID(name) template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T name(uint32_t, const T& v) { return v; }
 AQ_SCALAR_ID(max) AQ_SCALAR_ID(min) AQ_SCALAR_ID(avg) AQ_SCALAR_ID(sum) AQ_SCALAR_ID(maxs) AQ_SCALAR_ID(mins) AQ_SCALAR_ID(avgs)
-AQ_SCALAR_ID(sums) AQ_SCALAR_ID(last) AQ_SCALAR_ID(first) AQ_SCALAR_ID(prev) AQ_SCALAR_ID(aggnext)
+AQ_SCALAR_ID(sums) AQ_SCALAR_ID(last) AQ_SCALAR_ID(first) AQ_SCALAR_ID(prev) AQ_SCALAR_ID(aggnext) AQ_SCALAR_ID(median)
 AQ_SCALAR_ZERO(var) AQ_SCALAR_ZERO(vars) AQ_SCALAR_ZERO(stddev) AQ_SCALAR_ZERO(stddevs) AQ_SCALAR_ZERO(deltas)
 AQ_SCALAR_WID(maxw) AQ_SCALAR_WID(minw) AQ_SCALAR_WID(avgw) AQ_SCALAR_WID(sumw)
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T varw(uint32_t, const T&) { return 0; }

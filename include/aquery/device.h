@@ -324,7 +324,10 @@ public:
         if (rc != AQG_OK) die("aqg_gather", rc, ctx_);
         release(tmp); release(tmp2);
     }
-    // op(<per-group temporary>) at p: answered from the per-grouping cache (one kernel for all groups)
+    // op(<per-group temporary>) at p: answered from the per-grouping cache (one kernel for all groups).  op: an aqg_redop, or
+    // DEFERRED_MEDIAN (`median(col[vecs[g]])`: aqg_grouped_median / aqg_grouped_median_flat, result in the column's own type)
+    static constexpr int DEFERRED_MEDIAN = 1000;
+    size_t grouped_calls = 0;      // aqg_grouped_reduce / _reduce_flat / _median / _median_flat calls made so far (the tests count them)
     bool deferred_reduce(const void* p, int op, void* out16) {
         Entry* ep = deferred_at(p);
         if (!ep) return false;
@@ -334,19 +337,22 @@ public:
         auto hit = c->cache.find(key);
         if (hit == c->cache.end()) {
             const int tag = c->vcols[e.dv].tag;
-            const int ot = aqg_reduce_out_dtype(op, tag);
+            const bool med = op == DEFERRED_MEDIAN;
+            const int ot = med ? tag : aqg_reduce_out_dtype(op, tag);
             const size_t osz = aqg_dtype_size(ot);
             void* dout = nullptr;
             int rc = aqg_malloc(ctx(), (size_t)c->G * 16 + 16, &dout);
             if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+            ++grouped_calls;
             if (c->vcols[e.dv].layout == 1) {
-                rc = aqg_grouped_reduce_flat(ctx_, c->handle, op, tag, c->vcols[e.dv].dptr, dout);
-                if (rc != AQG_OK) die("aqg_grouped_reduce_flat", rc, ctx_);
+                rc = med ? aqg_grouped_median_flat(ctx_, c->handle, AQG_SEL_LOWER, tag, c->vcols[e.dv].dptr, dout)
+                         : aqg_grouped_reduce_flat(ctx_, c->handle, op, tag, c->vcols[e.dv].dptr, dout);
+                if (rc != AQG_OK) die(med ? "aqg_grouped_median_flat" : "aqg_grouped_reduce_flat", rc, ctx_);
             } else {
                 void* tmp = nullptr;
                 const void* dsrc = vcol_row_ptr(c, e.dv, &tmp);
-                rc = aqg_grouped_reduce(ctx_, c->handle, op, tag, dsrc, dout);
-                if (rc != AQG_OK) die("aqg_grouped_reduce", rc, ctx_);
+                rc = med ? aqg_grouped_median(ctx_, c->handle, AQG_SEL_LOWER, tag, dsrc, dout) : aqg_grouped_reduce(ctx_, c->handle, op, tag, dsrc, dout);
+                if (rc != AQG_OK) die(med ? "aqg_grouped_median" : "aqg_grouped_reduce", rc, ctx_);
                 release(tmp);
             }
             std::vector<unsigned char> packed((size_t)c->G * osz), slots((size_t)c->G * 16, 0);
