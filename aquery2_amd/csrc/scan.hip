@@ -6,8 +6,9 @@
 // Prefix scans: reduce-then-scan over 2048-element tiles (tile reduce -> one-workgroup scan of the
 // tile aggregates -> tile scan with carry-in); inside a tile: 8 consecutive elements per lane,
 // wavefront inclusive scan (__shfl_up over 64 lanes), LDS combine of the 4 waves.
-// Windows: every tile stages its elements plus a (w-1)-element halo in LDS; sums use the tile-local
-// prefix difference S[i]-S[i-w] (exact for integers), min/max use log2(w) LDS doubling steps.
+// Windows (scan_window.hpp, shared with the per-group scans of segscan.hip): every tile stages its elements plus a (w-1)-element
+// halo in LDS; sums use the tile-local prefix difference S[i]-S[i-w] (exact for integers), min/max use log2(w) LDS doubling steps;
+// long min/max windows of aligned columns take the van Herk kernel below.
 // Variances work on differences from an anchor taken from the data (mom_alg, scan_dev.hpp): short windows by two passes over the
 // window, running variances and longer windows from prefix moments about the first element.
 // Integer results are exact (bit-identical to the reference); floating sums follow a tree order.
@@ -16,6 +17,7 @@
 #include "dev_common.hpp"
 #include "chain_dev.hpp"
 #include "scan_dev.hpp"
+#include "scan_window.hpp"
 
 namespace {
 using namespace aqgscan;
@@ -244,169 +246,8 @@ __global__ void __launch_bounds__(SB) shift_kernel(const T* __restrict__ x, uint
     }
 }
 
-// ---- sliding sums: tile + halo in LDS, prefix difference -------------------------------------------
-// MODE 0 sumw (LongType out) / 1 avgw (double)
-template <class T, int MODE>
-__global__ void __launch_bounds__(SB) window_sum_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, void* __restrict__ out) {
-    using ALG = sum_alg<T>;
-    using A = typename ALG::A;
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    __shared__ A lds_w[8];
-    const uint32_t tile_start = blockIdx.x * TS, tile_end = tile_start + TS < n ? tile_start + TS : n;
-    // LDS position p <-> row tile_start - H + p, with the halo H = w - 1 rounded up to whole blocks of IT rows; rows before
-    // row 0 count as zeros, so the growing prefix of the first w rows needs no special case below
-    const uint32_t H = (w - 1 + IT - 1) / IT * IT;
-    const uint32_t L = H + TS, nblk = L / IT;
-    A* S = reinterpret_cast<A*>(smem_raw);                       // inclusive prefix of x over the extended tile
-    // a lane takes blocks of IT consecutive rows straight from HBM (vector load), scans them in registers and writes the
-    // prefixes to LDS once; blocks beyond the first SB (the halo's worth) take further rounds with a running carry
-    A carry = ALG::identity();
-    for (uint32_t blk0 = 0; blk0 < nblk; blk0 += SB) {
-        const uint32_t blk = blk0 + threadIdx.x;
-        const int64_t g0 = (int64_t)tile_start - (int64_t)H + (int64_t)blk * IT;
-        T v[IT];
-        if (blk < nblk && g0 >= 0 && g0 + IT <= (int64_t)n && (((uintptr_t)(x + g0)) & (sizeof(T) * IT > 16 ? 15 : sizeof(T) * IT - 1)) == 0) {
-            pack<T, IT> pk = *reinterpret_cast<const pack<T, IT>*>(x + g0);
-#pragma unroll
-            for (int j = 0; j < IT; ++j) v[j] = pk.v[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < IT; ++j) { const int64_t g = g0 + j; v[j] = (blk < nblk && g >= 0 && g < (int64_t)n) ? x[g] : (T)0; }
-        }
-        A loc[IT];
-        A a = ALG::identity();
-#pragma unroll
-        for (int j = 0; j < IT; ++j) { a = ALG::op(a, ALG::lift(v[j])); loc[j] = a; }
-        A tot;
-        A excl = ALG::op(carry, block_scan_excl<ALG>(a, lds_w, tot));
-        if (blk < nblk) {
-#pragma unroll
-            for (int j = 0; j < IT; ++j) S[blk * IT + j] = ALG::op(excl, loc[j]);
-        }
-        carry = ALG::op(carry, tot);
-    }
-    __syncthreads();
-    for (uint32_t i = tile_start + threadIdx.x; i < tile_end; i += SB) {
-        const uint32_t idx = i - tile_start + H;
-        const uint32_t len = i + 1 < w ? i + 1 : w;               // growing prefix for i < w
-        A s = idx >= len ? ALG::sub(S[idx], S[idx - len]) : S[idx];
-        if constexpr (MODE == 0) {
-            if constexpr (std::is_floating_point_v<T>) static_cast<double*>(out)[i] = s;
-            else static_cast<aqg_i128*>(out)[i] = ALG::to_i128(s);
-        } else {
-            static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
-        }
-    }
-}
-
-// floating inputs, short windows: add the window's elements directly (oldest first) -- no prefix cancellation
-template <class T, int MODE>
-__global__ void __launch_bounds__(SB) window_direct_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, double* __restrict__ out) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t len = i + 1 < w ? i + 1 : w;
-        double s = 0;
-        for (uint32_t j = i + 1 - len; j <= i; ++j) s += (double)x[j];
-        out[i] = MODE == 0 ? s : s / (double)len;
-    }
-}
-
-// ---- sliding min / max: tile + halo in LDS, doubling, eight elements per lane ---------------------------------------------
-// M_k[p] = best of the 2^k elements ending at p; M_{k+1}[p] = better(M_k[p], M_k[p - 2^k]); the window of length w is
-// better(M_K[p], M_K[p - (w - 2^K)]) with 2^K <= w < 2^(K+1).  A lane works on blocks of eight consecutive positions: the levels
-// with 2^k < 8 happen in registers in one step (block + predecessor block), every later level reads its neighbour block with
-// 16-byte LDS loads (positions are laid out so that blocks are 16-byte aligned).  Positions before row 0 hold the identity, so
-// the growing prefix of the first w rows needs no special case.  (Element-at-a-time doubling: minw(100) ran at 34 % of the
-// HBM roofline, bounded by LDS instructions.)
-template <class T, bool IS_MAX>
-__global__ void __launch_bounds__(SB) window_minmax_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, T* __restrict__ out) {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    constexpr int E = 8;
-    struct alignas(E * sizeof(T) > 16 ? 16 : E * sizeof(T)) blk_t { T v[E]; };
-    const uint32_t tile_start = blockIdx.x * TS;
-    const uint32_t H = (w - 1 + E - 1) / E * E;                   // halo, rounded up to whole blocks
-    const uint32_t L = H + TS;                                    // LDS position p <-> row tile_start - H + p
-    T* M0 = reinterpret_cast<T*>(smem_raw);
-    T* M1 = M0 + L;
-    T ident;
-    if constexpr (std::is_floating_point_v<T>) ident = IS_MAX ? -(T)INFINITY : (T)INFINITY;
-    else ident = IS_MAX ? dlimits<T>::min() : dlimits<T>::max();
-    auto better = [](T a, T b) { if constexpr (IS_MAX) return b > a ? b : a; else return b < a ? b : a; };
-    for (uint32_t p = threadIdx.x; p < H; p += SB) {
-        const int64_t g = (int64_t)tile_start - (int64_t)H + p;
-        M0[p] = g >= 0 ? x[g] : ident;                            // g < tile_start <= n - 1
-    }
-    {
-        const uint32_t g0 = tile_start + threadIdx.x * E;         // TS == SB * E: one block of the tile per lane
-        blk_t b;
-        if (g0 + E <= n && (reinterpret_cast<uintptr_t>(x + g0) & (alignof(blk_t) - 1)) == 0) b = *reinterpret_cast<const blk_t*>(x + g0);
-        else {
-#pragma unroll
-            for (int q = 0; q < E; ++q) b.v[q] = g0 + q < n ? x[g0 + q] : ident;
-        }
-        *reinterpret_cast<blk_t*>(M0 + H + threadIdx.x * E) = b;
-    }
-    __syncthreads();
-    uint32_t K = 0;
-    while ((2u << K) <= w) ++K;                                    // 2^K <= w < 2^(K+1)
-    const uint32_t KA = K < 3 ? K : 3;
-    const uint32_t nblk = L / E;
-    T* cur = M0; T* nxt = M1;
-    if (KA) {                                                      // levels 0 .. KA-1 in registers
-        for (uint32_t blk = threadIdx.x; blk < nblk; blk += SB) {
-            T a[2 * E];
-            const blk_t own = *reinterpret_cast<const blk_t*>(cur + blk * E);
-            blk_t prev;
-            if (blk) prev = *reinterpret_cast<const blk_t*>(cur + (blk - 1) * E);
-#pragma unroll
-            for (int q = 0; q < E; ++q) { a[q] = blk ? prev.v[q] : ident; a[E + q] = own.v[q]; }
-#pragma unroll
-            for (uint32_t k = 0; k < 3; ++k) {
-                if (k < KA) {
-                    const int d = 1 << k;
-#pragma unroll
-                    for (int j = 2 * E - 1; j >= d; --j) a[j] = better(a[j], a[j - d]);
-                }
-            }
-            blk_t o;
-#pragma unroll
-            for (int q = 0; q < E; ++q) o.v[q] = a[E + q];
-            *reinterpret_cast<blk_t*>(nxt + blk * E) = o;
-        }
-        __syncthreads();
-        T* t = cur; cur = nxt; nxt = t;
-    }
-    for (uint32_t k = KA; k < K; ++k) {                            // 2^k is a multiple of the block: aligned neighbour blocks
-        const uint32_t db = (1u << k) / E;
-        for (uint32_t blk = threadIdx.x; blk < nblk; blk += SB) {
-            blk_t a = *reinterpret_cast<const blk_t*>(cur + blk * E);
-            if (blk >= db) {
-                const blk_t b = *reinterpret_cast<const blk_t*>(cur + (blk - db) * E);
-#pragma unroll
-                for (int q = 0; q < E; ++q) a.v[q] = better(a.v[q], b.v[q]);
-            }
-            *reinterpret_cast<blk_t*>(nxt + blk * E) = a;
-        }
-        __syncthreads();
-        T* t = cur; cur = nxt; nxt = t;
-    }
-    const uint32_t off = w - (1u << K);                            // second span ends off positions earlier (0 <= off < 2^K, off <= H)
-    const uint32_t p0 = H + threadIdx.x * E, g0 = tile_start + threadIdx.x * E;
-    if (g0 < n) {
-        blk_t a = *reinterpret_cast<const blk_t*>(cur + p0);
-        if (off) {
-#pragma unroll
-            for (int q = 0; q < E; ++q) a.v[q] = better(a.v[q], cur[p0 + q - off]);
-        }
-        if (g0 + E <= n && (reinterpret_cast<uintptr_t>(out + g0) & (alignof(blk_t) - 1)) == 0) *reinterpret_cast<blk_t*>(out + g0) = a;
-        else {
-#pragma unroll
-            for (int q = 0; q < E; ++q) if (g0 + q < n) out[g0 + q] = a.v[q];
-        }
-    }
-}
-
 // ---- sliding min / max, long windows (w >= 128): van Herk / Gil-Werman ------------------------------------------------------------
-// The doubling kernel above pays log2(w) LDS passes over tile + halo (maxw(1000): nine, 34 % of the HBM roofline).  Here the LDS
+// The doubling kernel (window_minmax_kernel, scan_window.hpp) pays log2(w) LDS passes over tile + halo (maxw(1000): nine, 34 % of the HBM roofline).  Here the LDS
 // positions are cut into segments of w; with F[p] = best of [segment start, p] and B[p] = best of [p, segment end], the window of
 // length w ending at p is better(B[p - w + 1], F[p]) -- three passes whatever w is.  A workgroup of 1024 lanes holds C x 1024 positions
 // (halo rounded up to a 16-byte vector, then the tile); a lane owns C consecutive positions (C odd: the strided LDS accesses of a
@@ -415,7 +256,6 @@ __global__ void __launch_bounds__(SB) window_minmax_kernel(const T* __restrict__
 // through v_readlane, the 16 wavefront totals through LDS and one more 16-lane row scan.  The kernel is bound by VALU issue
 // (one wave64 instruction per cycle and CU: ~40 per element leave 70 % of the HBM roofline), which is why the scans avoid
 // ds_bpermute shuffles and per-wavefront loops.
-template <class T, bool IS_MAX> __device__ inline T vh_better(T a, T b) { if constexpr (IS_MAX) return b > a ? b : a; else return b < a ? b : a; }
 template <int CTRL> __device__ inline uint32_t vh_dpp32(uint32_t old, uint32_t src) { return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, CTRL, 0xF, 0xF, false); }
 // lane i <- lane i -/+ N of its 16-lane row (CTRL 0x110 + N: row_shr, 0x100 + N: row_shl); lanes without a source keep `old`
 template <int CTRL, class T> __device__ inline T vh_dpp(T old, T src) {
@@ -437,7 +277,7 @@ template <class T> __device__ inline T vh_readlane(T v, int l) {
 // inclusive segmented scan over the 16-lane rows: UP = towards higher lanes (prefix), else towards lower lanes (suffix)
 template <class T, bool IS_MAX, bool UP> __device__ inline void vh_row_scan(T& v, uint32_t& f, T ident) {
 #define AQG_VH_STEP(N) { const T ov = vh_dpp<(UP ? 0x110 : 0x100) + N>(ident, v); const uint32_t of = vh_dpp32<(UP ? 0x110 : 0x100) + N>(0u, f); \
-                         if (!f) v = vh_better<T, IS_MAX>(ov, v); f |= of; }
+                         if (!f) v = minmax_alg<T, IS_MAX>::op(ov, v); f |= of; }
     AQG_VH_STEP(1) AQG_VH_STEP(2) AQG_VH_STEP(4) AQG_VH_STEP(8)
 #undef AQG_VH_STEP
 }
@@ -452,9 +292,7 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
     __shared__ uint32_t wf[2][16];
     const uint32_t Hp = L - tile_rows;                            // halo (>= w - 1, a multiple of V like tile_rows)
     const uint64_t tile_start = (uint64_t)blockIdx.x * tile_rows;
-    T ident;
-    if constexpr (std::is_floating_point_v<T>) ident = IS_MAX ? -(T)INFINITY : (T)INFINITY;
-    else ident = IS_MAX ? dlimits<T>::min() : dlimits<T>::max();
+    const T ident = minmax_alg<T, IS_MAX>::identity();
     struct alignas(16) vec_t { T v[V]; };
     const bool oal = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     // position p <-> row tile_start - Hp + p (x is 16-byte aligned: the host sends other columns to the doubling kernel)
@@ -479,7 +317,7 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
     for (int j = 1; j < C; ++j) {
         const bool start = r0 + j == w;
         if (start) jf = j;
-        f[j] = start ? a[j] : vh_better<T, IS_MAX>(f[j - 1], a[j]);
+        f[j] = start ? a[j] : minmax_alg<T, IS_MAX>::op(f[j - 1], a[j]);
     }
     // backward: bk[j] = best of [p0 + j, min(segment end, p0 + C - 1)]; je = last index that ends a segment (-1: none)
     int je = -1;
@@ -489,7 +327,7 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
     for (int j = C - 2; j >= 0; --j) {
         const bool end = r0 + j + 1 == w;
         if (end && je < 0) je = j;
-        bk[j] = end ? a[j] : vh_better<T, IS_MAX>(bk[j + 1], a[j]);
+        bk[j] = end ? a[j] : minmax_alg<T, IS_MAX>::op(bk[j + 1], a[j]);
     }
     // ---- carries inside the wavefront: row scans, then the totals of the rows before (F) / behind (B) ----
     T fv = f[C - 1]; uint32_t ff = jf < C;
@@ -500,23 +338,23 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
     {
         const T t0 = vh_readlane(fv, 15), t1 = vh_readlane(fv, 31), t2 = vh_readlane(fv, 47);
         const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane((int)ff, 15), g1 = (uint32_t)__builtin_amdgcn_readlane((int)ff, 31), g2 = (uint32_t)__builtin_amdgcn_readlane((int)ff, 47);
-        const T c1 = t0, c2 = g1 ? t1 : vh_better<T, IS_MAX>(c1, t1), c3 = g2 ? t2 : vh_better<T, IS_MAX>(c2, t2);
+        const T c1 = t0, c2 = g1 ? t1 : minmax_alg<T, IS_MAX>::op(c1, t1), c3 = g2 ? t2 : minmax_alg<T, IS_MAX>::op(c2, t2);
         fcr = row == 0 ? ident : row == 1 ? c1 : row == 2 ? c2 : c3;
         fgr = row == 0 ? 0u : row == 1 ? g0 : row == 2 ? (g0 | g1) : (g0 | g1 | g2);
         const T u3 = vh_readlane(bv, 48), u2 = vh_readlane(bv, 32), u1 = vh_readlane(bv, 16);
         const uint32_t h3 = (uint32_t)__builtin_amdgcn_readlane((int)bf, 48), h2 = (uint32_t)__builtin_amdgcn_readlane((int)bf, 32), h1 = (uint32_t)__builtin_amdgcn_readlane((int)bf, 16);
-        const T d2 = u3, d1 = h2 ? u2 : vh_better<T, IS_MAX>(d2, u2), d0 = h1 ? u1 : vh_better<T, IS_MAX>(d1, u1);
+        const T d2 = u3, d1 = h2 ? u2 : minmax_alg<T, IS_MAX>::op(d2, u2), d0 = h1 ? u1 : minmax_alg<T, IS_MAX>::op(d1, u1);
         bcr = row == 3 ? ident : row == 2 ? d2 : row == 1 ? d1 : d0;
         bgr = row == 3 ? 0u : row == 2 ? h3 : row == 1 ? (h3 | h2) : (h3 | h2 | h1);
     }
     // this lane's EXCLUSIVE value inside the wavefront (the lane before / behind; across a row border: what enters the row)
     T fe = vh_dpp<0x111>(fcr, fv); uint32_t fef = vh_dpp32<0x111>(fgr, ff);
     T be = vh_dpp<0x101>(bcr, bv); uint32_t bef = vh_dpp32<0x101>(bgr, bf);
-    if ((lane & 15) != 0) { if (!fef) fe = vh_better<T, IS_MAX>(fcr, fe); fef |= fgr; }
-    if ((lane & 15) != 15) { if (!bef) be = vh_better<T, IS_MAX>(bcr, be); bef |= bgr; }
+    if ((lane & 15) != 0) { if (!fef) fe = minmax_alg<T, IS_MAX>::op(fcr, fe); fef |= fgr; }
+    if ((lane & 15) != 15) { if (!bef) be = minmax_alg<T, IS_MAX>::op(bcr, be); bef |= bgr; }
     // wavefront totals
-    if (lane == 63) { wv[0][wave] = ff ? fv : vh_better<T, IS_MAX>(fcr, fv); wf[0][wave] = ff | fgr; }
-    if (lane == 0) { wv[1][wave] = bf ? bv : vh_better<T, IS_MAX>(bcr, bv); wf[1][wave] = bf | bgr; }
+    if (lane == 63) { wv[0][wave] = ff ? fv : minmax_alg<T, IS_MAX>::op(fcr, fv); wf[0][wave] = ff | fgr; }
+    if (lane == 0) { wv[1][wave] = bf ? bv : minmax_alg<T, IS_MAX>::op(bcr, bv); wf[1][wave] = bf | bgr; }
     __syncthreads();
     // ---- carries between the wavefronts: the 16 totals, scanned in a 16-lane row; wavefront W takes lane W - 1 (F) / W + 1 (B) ----
     T fc = ident, bc = ident;
@@ -530,12 +368,12 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
         const T got2 = vh_readlane(sv, wave < 15 ? wave + 1 : 15);
         if (wave < 15) bc = got2;
     }
-    const T fcar = fef ? fe : vh_better<T, IS_MAX>(fc, fe);
-    const T bcar = bef ? be : vh_better<T, IS_MAX>(bc, be);
+    const T fcar = fef ? fe : minmax_alg<T, IS_MAX>::op(fc, fe);
+    const T bcar = bef ? be : minmax_alg<T, IS_MAX>::op(bc, be);
 #pragma unroll
     for (int j = 0; j < C; ++j) {
-        if (j < jf) f[j] = vh_better<T, IS_MAX>(fcar, f[j]);
-        if (j > je) bk[j] = vh_better<T, IS_MAX>(bcar, bk[j]);
+        if (j < jf) f[j] = minmax_alg<T, IS_MAX>::op(fcar, f[j]);
+        if (j > je) bk[j] = minmax_alg<T, IS_MAX>::op(bcar, bk[j]);
         Bs[p0 + j] = bk[j];
     }
     __syncthreads();
@@ -543,7 +381,7 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
 #pragma unroll
     for (int j = 0; j < C; ++j) {
         const uint32_t p = p0 + j;
-        if (p >= Hp) A[p] = vh_better<T, IS_MAX>(Bs[p - back], f[j]);
+        if (p >= Hp) A[p] = minmax_alg<T, IS_MAX>::op(Bs[p - back], f[j]);
     }
     __syncthreads();
     for (uint32_t q = threadIdx.x; q < tile_rows / V; q += NT) {
@@ -558,37 +396,7 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
     }
 }
 
-// large-window fallback for min/max: doubling passes through HBM (ping-pong), then the two-span combine
-template <class T, bool IS_MAX>
-__global__ void __launch_bounds__(SB) doubling_pass_kernel(const T* __restrict__ src, T* __restrict__ dst, uint32_t n, uint32_t d) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        T a = src[i];
-        if (i >= d) { T b = src[i - d]; if constexpr (IS_MAX) a = b > a ? b : a; else a = b < a ? b : a; }
-        dst[i] = a;
-    }
-}
-template <class T, bool IS_MAX>
-__global__ void __launch_bounds__(SB) doubling_final_kernel(const T* __restrict__ m, T* __restrict__ out, uint32_t n, uint32_t w, uint32_t span) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t len = i + 1 < w ? i + 1 : w;
-        T a = m[i];
-        if (len > span) { T b = m[i - (len - span)]; if constexpr (IS_MAX) a = b > a ? b : a; else a = b < a ? b : a; }
-        out[i] = a;
-    }
-}
-// large-window fallback for sums: out[i] = S[i] - S[i-len] over a global inclusive prefix (8-byte accumulators)
-template <class T, int MODE>
-__global__ void __launch_bounds__(SB) prefix_diff_kernel(const typename sum_alg<T>::A* __restrict__ S, uint32_t n, uint32_t w, void* __restrict__ out) {
-    using ALG = sum_alg<T>;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t len = i + 1 < w ? i + 1 : w;
-        auto s = i >= len ? ALG::sub(S[i], S[i - len]) : S[i];
-        if constexpr (MODE == 0) {
-            if constexpr (std::is_floating_point_v<T>) static_cast<double*>(out)[i] = s; else static_cast<aqg_i128*>(out)[i] = ALG::to_i128(s);
-        } else static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
-    }
-}
-// inclusive prefix in accumulator form (used by the fallback above)
+// inclusive prefix in accumulator form (the wide-window fallback of sumw / avgw: prefix_diff_kernel)
 template <class T>
 __global__ void __launch_bounds__(SB) tile_scan_raw_kernel(const T* __restrict__ x, uint32_t n, const typename sum_alg<T>::A* __restrict__ tile_prefix,
                                                            typename sum_alg<T>::A* __restrict__ out) {
@@ -633,12 +441,6 @@ __global__ void __launch_bounds__(SB) var_scan_kernel(const T* __restrict__ x, u
     }
     store_tile_striped(static_cast<O*>(out), blockIdx.x * TS, o, n, reinterpret_cast<O*>(stage_raw));
 }
-// varw / stddevw, windows of up to VAR_DIRECT_MAX_W: one tile per workgroup (var_short_tile)
-template <class T, bool SD, int RW>
-__global__ void __launch_bounds__(SB) var_short_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, double* __restrict__ out) {
-    __shared__ T L[TS + VAR_DIRECT_MAX_W];
-    var_short_tile<T, SD, RW>(x, n, w, [&](uint32_t p) { return p + 1 < w ? p + 1 : w; }, L, out);
-}
 // the moments scan of a whole column: WR as var_scan_kernel (workspace reset and sized by the caller)
 template <class T, int WR> int run_var_scan(aqg_ctx* ctx, const T* x, uint32_t n, void* out, bool timed = true) {
     using A = typename mom_alg<T>::A;
@@ -661,35 +463,45 @@ size_t var_ws_bytes(uint32_t n) {
 template <class T, bool IS_MAX> __global__ void __launch_bounds__(SB) apply_seed_kernel(T* __restrict__ out, uint32_t n, T seed) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { const T v = out[i]; out[i] = IS_MAX ? (seed > v ? seed : v) : (seed < v ? seed : v); }
 }
-template <class T, class ALG, int WR>
-int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& seed = ScanSeed{{0, 0}, -0.0, 0}, const T* mm_seed = nullptr) {
-    using A = typename ALG::A;
-    uint32_t ntiles = aqg_ceil_div(n, TS);
-    constexpr int M = chain_m<T>();
-    const uint32_t nlinks = (ntiles + M - 1) / M;
-    constexpr size_t osz = WR == W_SUMS ? (std::is_floating_point_v<T> ? 8 : 16) : WR == W_AVGS ? 8 : sizeof(T);
+// workspace of one prefix scan, either form (resets it)
+template <class A> int prefix_ws(aqg_ctx* ctx, uint32_t ntiles) {
     constexpr int PW = std::is_same_v<A, aqg_i128> ? 2 : 1;
     AQG_TRY(aqg_ws_reset(ctx));
-    AQG_TRY(aqg_ws_ensure(ctx, (size_t)ntiles * (4 + 16 * PW + sizeof(A)) + ((size_t)ntiles / CH + 2) * sizeof(A) + 16384));
-    // Measured at 1e9 int32 rows (whole call): mins 1.53 ms chained vs 3.17 ms three-kernel; sums 4.34 vs 4.09; avgs 2.94 vs 2.75.
-    // A 4-byte aggregate is handed over in one flagged word; the 8-byte sum of an int32 column takes two words per link and
-    // the look-back then costs 1.0 ms at 1e9 rows (the same kernel without any look-back: sums 3.35 ms, avgs 2.30 ms).
-    // Packing that sum into one 62-bit word changed nothing (4.43 ms): at two workgroups per CU (the 16-byte results take the
-    // registers) the look-back latency itself is exposed, not the number of words.
-    constexpr bool use_chain = WR == W_MINS || WR == W_MAXS || WR == W_MAXP || WR == W_MINP;
+    return aqg_ws_ensure(ctx, (size_t)ntiles * (4 + 16 * PW + sizeof(A)) + ((size_t)ntiles / CH + 2) * sizeof(A) + 16384);
+}
+template <class T, int WR> constexpr size_t prefix_out_size() { return WR == W_SUMS ? (std::is_floating_point_v<T> ? 8 : 16) : WR == W_AVGS ? 8 : sizeof(T); }
+// Measured at 1e9 int32 rows (whole call): mins 1.53 ms chained vs 3.17 ms three-kernel; sums 4.34 vs 4.09; avgs 2.94 vs 2.75.
+// A 4-byte aggregate is handed over in one flagged word; the 8-byte sum of an int32 column takes two words per link and
+// the look-back then costs 1.0 ms at 1e9 rows (the same kernel without any look-back: sums 3.35 ms, avgs 2.30 ms).
+// Packing that sum into one 62-bit word changed nothing (4.43 ms): at two workgroups per CU (the 16-byte results take the
+// registers) the look-back latency itself is exposed, not the number of words.
+// So sums / avgs take the three kernels (run_prefix) and the running min / max the chain (run_chained).
+template <class T, class ALG, int WR>
+int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& seed = ScanSeed{{0, 0}, -0.0, 0}) {
+    using A = typename ALG::A;
+    const uint32_t ntiles = aqg_ceil_div(n, TS);
+    constexpr size_t osz = prefix_out_size<T, WR>();
+    AQG_TRY(prefix_ws<A>(ctx, ntiles));
+    A *agg3, *chunk_tot;
+    AQG_TRY(aqg_ws_get(ctx, ntiles, &agg3));
+    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles / CH + 2, &chunk_tot));
+    hipLaunchKernelGGL((tile_reduce_kernel<T, ALG>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg3);
+    launch_agg_scan<ALG>(ctx, agg3, ntiles, chunk_tot);
+    aqg_kernel_timer_begin(ctx);
+    hipLaunchKernelGGL((tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, agg3, out, seed);
+    aqg_kernel_timer_end(ctx);
+    return aqg_check_launch(ctx, "prefix scan");
+}
+// single pass (chained tiles); mm_seed: the fold of the rows of earlier shards (null: none)
+template <class T, class ALG, int WR>
+int run_chained(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const T* mm_seed = nullptr) {
+    using A = typename ALG::A;
+    const uint32_t ntiles = aqg_ceil_div(n, TS);
+    constexpr int M = chain_m<T>();
+    const uint32_t nlinks = (ntiles + M - 1) / M;
+    constexpr size_t osz = prefix_out_size<T, WR>();
     constexpr bool is_min = WR == W_MINS || WR == W_MINP;
-    if (!use_chain) {
-        A *agg3, *chunk_tot;
-        AQG_TRY(aqg_ws_get(ctx, ntiles, &agg3));
-        AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles / CH + 2, &chunk_tot));
-        hipLaunchKernelGGL((tile_reduce_kernel<T, ALG>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg3);
-        launch_agg_scan<ALG>(ctx, agg3, ntiles, chunk_tot);
-        aqg_kernel_timer_begin(ctx);
-        hipLaunchKernelGGL((tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, agg3, out, seed);
-        aqg_kernel_timer_end(ctx);
-        return aqg_check_launch(ctx, "prefix scan");
-    }
-    // ---- single pass (chained tiles) --------------------------------------------------------------------------------
+    AQG_TRY(prefix_ws<A>(ctx, ntiles));
     uint32_t* ctrl;
     uint64_t* slots;
     constexpr int NW = flagged_words<A>();
@@ -698,12 +510,7 @@ int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& 
     AQG_HIP(ctx, hipMemsetAsync(ctrl, 0, 64, ctx->stream));
     AQG_HIP(ctx, hipMemsetAsync(slots, 0, (size_t)nlinks * NW * 8, ctx->stream));
     aqg_kernel_timer_begin(ctx);
-    if constexpr (use_chain) {
-        T none;                                              // the algebra's identity, spelled on the host
-        if constexpr (std::is_floating_point_v<T>) none = is_min ? (T)INFINITY : -(T)INFINITY;
-        else none = is_min ? dlimits<T>::max() : dlimits<T>::min();
-        hipLaunchKernelGGL((chained_scan_kernel<T, ALG, WR, M>), dim3(nlinks), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, ctrl, slots, out, mm_seed ? *mm_seed : none);
-    }
+    hipLaunchKernelGGL((chained_scan_kernel<T, ALG, WR, M>), dim3(nlinks), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, ctrl, slots, out, mm_seed ? *mm_seed : ALG::identity());
     aqg_kernel_timer_end(ctx);
     AQG_TRY(aqg_check_launch(ctx, "chained_scan_kernel"));
     uint32_t h[2] = {0, 0};
@@ -715,12 +522,30 @@ int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& 
     AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
     hipLaunchKernelGGL((tile_reduce_kernel<T, ALG>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg);
     hipLaunchKernelGGL((agg_scan_kernel<ALG>), dim3(1), dim3(SB), 0, ctx->stream, agg, ntiles);
-    hipLaunchKernelGGL((tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, agg, out, seed);
-    if constexpr (use_chain) {
-        if (mm_seed) hipLaunchKernelGGL((apply_seed_kernel<T, !is_min>), dim3(aqg_grid(ctx, n, SB, 4, 8)), dim3(SB), 0, ctx->stream, static_cast<T*>(out), n, *mm_seed);
-    }
+    hipLaunchKernelGGL((tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, agg, out, ScanSeed{{0, 0}, -0.0, 0});
+    if (mm_seed) hipLaunchKernelGGL((apply_seed_kernel<T, !is_min>), dim3(aqg_grid(ctx, n, SB, 4, 8)), dim3(SB), 0, ctx->stream, static_cast<T*>(out), n, *mm_seed);
     return aqg_check_launch(ctx, "prefix scan");
 }
+
+// what window_scan (scan_window.hpp) asks of a layout, for a whole column
+template <class T> struct column_windows {
+    using seg_t = whole_column;
+    using A = typename sum_alg<T>::A;
+    aqg_ctx* ctx; const T* x; uint32_t n; unsigned row_grid;
+    whole_column seg() const { return {}; }
+    int distances(whole_column&) { return AQG_OK; }                  // a row's distance to the start is its index
+    int reserve(size_t bytes) { AQG_TRY(aqg_ws_reset(ctx)); return aqg_ws_ensure(ctx, bytes + var_ws_bytes(n) + 8192); }   // (var_ws_bytes: the tile aggregates of either producer)
+    int raw_prefix(A* S) {
+        const uint32_t ntiles = aqg_ceil_div(n, TS);
+        A* agg;
+        AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
+        hipLaunchKernelGGL((tile_reduce_kernel<T, sum_alg<T>>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg);
+        hipLaunchKernelGGL((agg_scan_kernel<sum_alg<T>>), dim3(1), dim3(SB), 0, ctx->stream, agg, ntiles);
+        hipLaunchKernelGGL((tile_scan_raw_kernel<T>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg, S);
+        return AQG_OK;
+    }
+    int moments(dpair* P) { return run_var_scan<T, 2>(ctx, x, n, P, /*timed=*/false); }
+};
 
 } // namespace
 
@@ -771,10 +596,10 @@ int aqg_scan_minmax_seeded(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t
         if (seed_host) memcpy(&sd, seed_host, sizeof(T));
         const T* sp = seed_host ? &sd : nullptr;
         switch (op) {
-        case AQG_SCAN_MINS: return run_prefix<T, min_alg<T>, W_MINS>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
-        case AQG_SCAN_MINW: return run_prefix<T, min_alg<T>, W_MINP>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
-        case AQG_SCAN_MAXS: return run_prefix<T, max_alg<T>, W_MAXS>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
-        case AQG_SCAN_MAXW: return run_prefix<T, max_alg<T>, W_MAXP>(ctx, x, n, out, ScanSeed{{0, 0}, -0.0, 0}, sp);
+        case AQG_SCAN_MINS: return run_chained<T, min_alg<T>, W_MINS>(ctx, x, n, out, sp);
+        case AQG_SCAN_MINW: return run_chained<T, min_alg<T>, W_MINP>(ctx, x, n, out, sp);
+        case AQG_SCAN_MAXS: return run_chained<T, max_alg<T>, W_MAXS>(ctx, x, n, out, sp);
+        case AQG_SCAN_MAXW: return run_chained<T, max_alg<T>, W_MAXP>(ctx, x, n, out, sp);
         }
         return AQG_ERR_ARG;
     });
@@ -792,7 +617,6 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
     return aqg_dispatch_num(t, [&](auto tt) -> int {
         using T = typename decltype(tt)::type;
         const T* x = static_cast<const T*>(xv);
-        const uint32_t ntiles = aqg_ceil_div(n, TS);
         // shifts: an exact grid, ONE 16-byte vector per lane and workgroup (1e9 rows: deltas 1.59 -> 1.25 ms against a capped
         // grid-stride launch; 4 / 8 / 16 / 32 / 64 vectors per lane: 1.37 / 1.45 / 1.44 / 1.51 / 1.48 ms)
         auto shift_grid = [&](size_t out_size, unsigned per = 1) -> unsigned {
@@ -802,91 +626,35 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
             return (unsigned)(g < 1 ? 1 : g);
         };
         const unsigned sgrid = shift_grid(sizeof(T));
+        auto shift = [&](auto kern, unsigned grid, uint32_t ww, const char* what) -> int {
+            aqg_kernel_timer_begin(ctx);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(SB), 0, ctx->stream, x, n, ww, out);
+            aqg_kernel_timer_end(ctx);
+            return aqg_check_launch(ctx, what);
+        };
+        column_windows<T> col{ctx, x, n, sgrid};
         switch (op) {
         case AQG_SCAN_SUMS: return run_prefix<T, sum_alg<T>, W_SUMS>(ctx, x, n, out);
         case AQG_SCAN_AVGS: return run_prefix<T, sum_alg<T>, W_AVGS>(ctx, x, n, out);
-        case AQG_SCAN_MINS: return run_prefix<T, min_alg<T>, W_MINS>(ctx, x, n, out);
-        case AQG_SCAN_MAXS: return run_prefix<T, max_alg<T>, W_MAXS>(ctx, x, n, out);
-        case AQG_SCAN_DELTAS: aqg_kernel_timer_begin(ctx); hipLaunchKernelGGL((shift_kernel<T, AQG_SCAN_DELTAS>), dim3(sgrid), dim3(SB), 0, ctx->stream, x, n, w, out); aqg_kernel_timer_end(ctx); return aqg_check_launch(ctx, "deltas");
-        case AQG_SCAN_PREV: aqg_kernel_timer_begin(ctx); hipLaunchKernelGGL((shift_kernel<T, AQG_SCAN_PREV>), dim3(sgrid), dim3(SB), 0, ctx->stream, x, n, w, out); aqg_kernel_timer_end(ctx); return aqg_check_launch(ctx, "prev");
-        case AQG_SCAN_NEXT: aqg_kernel_timer_begin(ctx); hipLaunchKernelGGL((shift_kernel<T, AQG_SCAN_NEXT>), dim3(sgrid), dim3(SB), 0, ctx->stream, x, n, w, out); aqg_kernel_timer_end(ctx); return aqg_check_launch(ctx, "aggnext");
+        case AQG_SCAN_MINS: return run_chained<T, min_alg<T>, W_MINS>(ctx, x, n, out);
+        case AQG_SCAN_MAXS: return run_chained<T, max_alg<T>, W_MAXS>(ctx, x, n, out);
+        case AQG_SCAN_DELTAS: return shift(&shift_kernel<T, AQG_SCAN_DELTAS>, sgrid, w, "deltas");
+        case AQG_SCAN_PREV: return shift(&shift_kernel<T, AQG_SCAN_PREV>, sgrid, w, "prev");
+        case AQG_SCAN_NEXT: return shift(&shift_kernel<T, AQG_SCAN_NEXT>, sgrid, w, "aggnext");
         case AQG_SCAN_RATIOW: {
             // aggregations.h:172-175: a window not smaller than the column degrades to w = 1
             uint32_t len = n, ww = w;
             if (n <= ww) len = 1;
             ww = ww > len ? len : ww;
-            aqg_kernel_timer_begin(ctx);
-            hipLaunchKernelGGL((shift_kernel<T, AQG_SCAN_RATIOW>), dim3(shift_grid(sizeof(T) == 4 ? 4 : 8, 4)), dim3(SB), 0, ctx->stream, x, n, ww, out);   // (one vector per lane: 1.59 ms, four: 1.43 ms)
-            aqg_kernel_timer_end(ctx);
-            return aqg_check_launch(ctx, "ratiow");
+            return shift(&shift_kernel<T, AQG_SCAN_RATIOW>, shift_grid(sizeof(T) == 4 ? 4 : 8, 4), ww, "ratiow");   // (one vector per lane: 1.59 ms, four: 1.43 ms)
         }
-        case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: {
-            // the intended population variance of the last min(w, i + 1) rows (D9)
-            const uint32_t ww = w > n ? n : w;
-            const bool sd = op == AQG_SCAN_STDDEVW;
-            if (ww <= VAR_DIRECT_MAX_W) {
-                auto go = [&](auto kern) -> int {
-                    aqg_kernel_timer_begin(ctx);
-                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, ww, static_cast<double*>(out));
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "var_short_kernel");
-                };
-                if (ww <= (uint32_t)VAR_REG_W) return sd ? go(&var_short_kernel<T, true, VAR_REG_W>) : go(&var_short_kernel<T, false, VAR_REG_W>);
-                return sd ? go(&var_short_kernel<T, true, 0>) : go(&var_short_kernel<T, false, 0>);
-            }
-            AQG_TRY(aqg_ws_reset(ctx));
-            AQG_TRY(aqg_ws_ensure(ctx, var_ws_bytes(n) + (size_t)n * sizeof(dpair) + 256));
-            dpair* P;
-            AQG_TRY(aqg_ws_get(ctx, n, &P));
-            aqg_kernel_timer_begin(ctx);                                        // the timer spans every pass: moments scan, difference
-            AQG_TRY((run_var_scan<T, 2>(ctx, x, n, P, /*timed=*/false)));
-            if (sd) hipLaunchKernelGGL((var_prefix_diff_kernel<true>), dim3(sgrid), dim3(SB), 0, ctx->stream, P, (const uint32_t*)nullptr, n, ww, static_cast<double*>(out));
-            else hipLaunchKernelGGL((var_prefix_diff_kernel<false>), dim3(sgrid), dim3(SB), 0, ctx->stream, P, (const uint32_t*)nullptr, n, ww, static_cast<double*>(out));
-            aqg_kernel_timer_end(ctx);
-            return aqg_check_launch(ctx, "wide window variance");
-        }
-        case AQG_SCAN_SUMW: case AQG_SCAN_AVGW: {
-            using A = typename sum_alg<T>::A;
-            uint32_t ww = w > n ? n : w;                                        // w clamped to len (:241,264)
-            const size_t ext = (size_t)TS + (ww - 1 + IT - 1) / IT * IT;            // tile + halo rounded up to whole blocks
-            size_t lds = ext * sizeof(A);
-            if constexpr (std::is_floating_point_v<T>) {
-                if (ww <= 64) {
-                    aqg_kernel_timer_begin(ctx);
-                    if (op == AQG_SCAN_SUMW) hipLaunchKernelGGL((window_direct_kernel<T, 0>), dim3(sgrid), dim3(SB), 0, ctx->stream, x, n, ww, static_cast<double*>(out));
-                    else hipLaunchKernelGGL((window_direct_kernel<T, 1>), dim3(sgrid), dim3(SB), 0, ctx->stream, x, n, ww, static_cast<double*>(out));
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "window_direct_kernel");
-                }
-            }
-            if (lds <= HALO_MAX_BYTES) {
-                auto go = [&](auto kern) -> int {
-                    AQG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    aqg_kernel_timer_begin(ctx);
-                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), lds, ctx->stream, x, n, ww, out);
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "window_sum_kernel");
-                };
-                return op == AQG_SCAN_SUMW ? go(&window_sum_kernel<T, 0>) : go(&window_sum_kernel<T, 1>);
-            }
-            // wide window: global inclusive prefix, then the difference
-            AQG_TRY(aqg_ws_reset(ctx));
-            AQG_TRY(aqg_ws_ensure(ctx, (size_t)ntiles * sizeof(A) + (size_t)n * sizeof(A) + 8192));
-            A *agg, *S;
-            AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
-            AQG_TRY(aqg_ws_get(ctx, n, &S));
-            hipLaunchKernelGGL((tile_reduce_kernel<T, sum_alg<T>>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg);
-            hipLaunchKernelGGL((agg_scan_kernel<sum_alg<T>>), dim3(1), dim3(SB), 0, ctx->stream, agg, ntiles);
-            hipLaunchKernelGGL((tile_scan_raw_kernel<T>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg, S);
-            if (op == AQG_SCAN_SUMW) hipLaunchKernelGGL((prefix_diff_kernel<T, 0>), dim3(sgrid), dim3(SB), 0, ctx->stream, S, n, ww, out);
-            else hipLaunchKernelGGL((prefix_diff_kernel<T, 1>), dim3(sgrid), dim3(SB), 0, ctx->stream, S, n, ww, out);
-            return aqg_check_launch(ctx, "wide window sum");
-        }
+        case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: case AQG_SCAN_SUMW: case AQG_SCAN_AVGW:
+            return window_scan(ctx, col, op, x, n, w > n ? n : w, out);          // w clamped to len (:241,264)
         case AQG_SCAN_MINW: case AQG_SCAN_MAXW: {
             const bool is_max = op == AQG_SCAN_MAXW;
             // the deque never expires anything when w == 0 or w >= n: plain running min / max (no seed)
             uint32_t ww = (w == 0 || w > n) ? n : w;
-            if (ww == n) return is_max ? run_prefix<T, max_alg<T>, W_MAXP>(ctx, x, n, out) : run_prefix<T, min_alg<T>, W_MINP>(ctx, x, n, out);
+            if (ww == n) return is_max ? run_chained<T, max_alg<T>, W_MAXP>(ctx, x, n, out) : run_chained<T, min_alg<T>, W_MINP>(ctx, x, n, out);
             // long windows: van Herk / Gil-Werman over C x 1024 LDS positions (C odd; two arrays of them; two workgroups per CU while
             // they take <= 78 KB and the kernel keeps to 64 VGPRs).  Needs a 16-byte aligned column; others take the doubling kernel.
             if (ww >= 128 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && n >= 64) {
@@ -901,13 +669,7 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
                     const size_t vlds = (size_t)c * 2048 * sizeof(T);
                     const bool two = c <= CMAX2 && vlds <= 78 * 1024;
                     const unsigned vtiles = (unsigned)(((uint64_t)n + tile_rows - 1) / tile_rows);
-                    auto gov = [&](auto kern) -> int {
-                        AQG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlds));
-                        aqg_kernel_timer_begin(ctx);
-                        hipLaunchKernelGGL(kern, dim3(vtiles), dim3(1024), vlds, ctx->stream, x, n, ww, tile_rows, static_cast<T*>(out));
-                        aqg_kernel_timer_end(ctx);
-                        return aqg_check_launch(ctx, "window_minmax_vh_kernel");
-                    };
+                    auto gov = [&](auto kern) -> int { return launch_window(ctx, kern, vtiles, 1024, vlds, "window_minmax_vh_kernel", x, n, ww, tile_rows, static_cast<T*>(out)); };
                     auto byc = [&](auto mx) -> int {
                         constexpr bool MX = decltype(mx)::value;
                         if constexpr (sizeof(T) <= 4) {
@@ -929,36 +691,7 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
                     return is_max ? byc(std::true_type{}) : byc(std::false_type{});
                 }
             }
-            size_t lds = (size_t)(TS + (ww - 1 + 7) / 8 * 8) * sizeof(T) * 2;
-            if (lds <= HALO_MAX_BYTES) {
-                auto go = [&](auto kern) -> int {
-                    AQG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    aqg_kernel_timer_begin(ctx);
-                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), lds, ctx->stream, x, n, ww, static_cast<T*>(out));
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "window_minmax_kernel");
-                };
-                return is_max ? go(&window_minmax_kernel<T, true>) : go(&window_minmax_kernel<T, false>);
-            }
-            // wide window: doubling passes through HBM
-            AQG_TRY(aqg_ws_reset(ctx));
-            AQG_TRY(aqg_ws_ensure(ctx, (size_t)n * sizeof(T) * 2 + 8192));
-            T *b0, *b1;
-            AQG_TRY(aqg_ws_get(ctx, n, &b0));
-            AQG_TRY(aqg_ws_get(ctx, n, &b1));
-            uint32_t K = 0;
-            while ((2u << K) <= ww && K < 31) ++K;
-            const T* src = x;
-            T* dst = b0;
-            for (uint32_t k = 0; k < K; ++k) {
-                if (is_max) hipLaunchKernelGGL((doubling_pass_kernel<T, true>), dim3(sgrid), dim3(SB), 0, ctx->stream, src, dst, n, 1u << k);
-                else hipLaunchKernelGGL((doubling_pass_kernel<T, false>), dim3(sgrid), dim3(SB), 0, ctx->stream, src, dst, n, 1u << k);
-                src = dst;
-                dst = dst == b0 ? b1 : b0;
-            }
-            if (is_max) hipLaunchKernelGGL((doubling_final_kernel<T, true>), dim3(sgrid), dim3(SB), 0, ctx->stream, src, static_cast<T*>(out), n, ww, 1u << K);
-            else hipLaunchKernelGGL((doubling_final_kernel<T, false>), dim3(sgrid), dim3(SB), 0, ctx->stream, src, static_cast<T*>(out), n, ww, 1u << K);
-            return aqg_check_launch(ctx, "wide window min/max");
+            return window_scan(ctx, col, op, x, n, ww, out);
         }
         case AQG_SCAN_VARS: case AQG_SCAN_STDDEVS: {
             AQG_TRY(aqg_ws_reset(ctx));

@@ -1,10 +1,25 @@
 // scan_dev.hpp -- tile vocabulary shared by the scan kernels (scan.hip: whole columns; segscan.hip: per-group scans over the
-// flat row-list layout of a grouping): accumulator algebras, the workgroup exclusive scan, blocked tile loads and the
-// LDS-transposed tile store.
+// flat row-list layout of a grouping; scan_window.hpp: the sliding windows of both): accumulator algebras and the carry of a segmented
+// scan, the workgroup exclusive scan, blocked tile loads, the LDS-transposed tile store, the variance
+// vocabulary and the scan of the tile aggregates.
 #pragma once
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
 #include "chain_dev.hpp"
+
+// ---- the carry of a segmented scan -------------------------------------------------------------------------------------------
+// (in an unnamed namespace, like the kernels of the .hip files that use it: the type names go into the names of the kernels' LDS
+// variables, by which the compiler lays them out -- with them inside aqgscan the carry scans of segscan.hip compiled to other code)
+namespace {
+// v: fold of the values behind the last group start of the range (of the whole range when it has none); s: position + 1 of that
+// start (0: none); c: group starts in the range
+template <class A> struct SegCarry { A v; uint32_t s; uint32_t c; };
+template <class ALG> struct seg_alg {
+    using A = SegCarry<typename ALG::A>;
+    __device__ static A identity() { A r; r.v = ALG::identity(); r.s = 0; r.c = 0; return r; }
+    __device__ static A op(A a, A b) { A r; r.s = b.s ? b.s : a.s; r.c = a.c + b.c; r.v = b.s ? b.v : ALG::op(a.v, b.v); return r; }
+};
+} // namespace
 
 namespace aqgscan {
 
@@ -72,16 +87,17 @@ template <class T> struct sum_alg {
 // row into max().  The reference's seeds (mins: max(), maxs / max: numeric_limits<T>::min()) are applied where a result is written.
 template <class T> struct min_alg {
     using A = T;
-    __device__ static A identity() { if constexpr (std::is_floating_point_v<T>) return (T)INFINITY; else return dlimits<T>::max(); }
+    __host__ __device__ static A identity() { if constexpr (std::is_floating_point_v<T>) return (T)INFINITY; else return dlimits<T>::max(); }
     __device__ static A lift(T v) { return v; }
     __device__ static A op(A a, A b) { return b < a ? b : a; }
 };
 template <class T> struct max_alg {
     using A = T;
-    __device__ static A identity() { if constexpr (std::is_floating_point_v<T>) return -(T)INFINITY; else return dlimits<T>::min(); }
+    __host__ __device__ static A identity() { if constexpr (std::is_floating_point_v<T>) return -(T)INFINITY; else return dlimits<T>::min(); }
     __device__ static A lift(T v) { return v; }
     __device__ static A op(A a, A b) { return b > a ? b : a; }
 };
+template <class T, bool IS_MAX> using minmax_alg = std::conditional_t<IS_MAX, max_alg<T>, min_alg<T>>;
 
 // exclusive scan of one value per lane across the workgroup; `total` = fold of all lanes
 template <class ALG, class A> __device__ inline A block_scan_excl(A v, A* lds_w /* >= 5 */, A& total) {
@@ -143,21 +159,6 @@ template <class T> __device__ inline aqg_i128 first_row_rounding(T v) {
         return i128_from_i64((int64_t)((uint64_t)(int64_t)d - (uint64_t)v));
     }
 }
-template <class T> struct dsum_alg {
-    using A = double;
-    __device__ static double identity() { return 0; }
-    __device__ static double lift(T v) { return (double)v; }
-    __device__ static double op(double a, double b) { return a + b; }
-    __device__ static double sub(double a, double b) { return a - b; }
-    __device__ static double to_double(double a) { return a; }
-    __device__ static aqg_i128 to_i128(double) { return {0, 0}; }
-};
-template <class T> struct sq_alg {   // tile aggregate of x*x in double
-    using A = double;
-    __device__ static double identity() { return 0; }
-    __device__ static double lift(T v) { return (double)v * (double)v; }
-    __device__ static double op(double a, double b) { return a + b; }
-};
 struct dpair { double s, q; };
 
 // ---- variance scans (vars / stddevs / varw / stddevw) --------------------------------------------------------------------------
@@ -237,19 +238,6 @@ __device__ inline void var_short_tile(const T* __restrict__ x, uint32_t n, uint3
         out[p] = SD ? sqrt(var) : var;
     }
 }
-// windows of any length: P[i] = anchored sums of x over [first of the group (of the column when D is null) .. i], one anchor per
-// group; the window is the difference of two of them.  D[i] = predecessors of i inside its group.
-template <bool SD>
-__global__ void __launch_bounds__(SB) var_prefix_diff_kernel(const dpair* __restrict__ P, const uint32_t* __restrict__ D, uint32_t n, uint32_t w, double* __restrict__ out) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t d = D ? D[i] : i, len = d + 1 < w ? d + 1 : w;
-        dpair a = P[i];
-        if (len <= d) { const dpair b = P[i - len]; a.s -= b.s; a.q -= b.q; }
-        const double v = var_from(a.s, a.q, (double)len);
-        out[i] = SD ? sqrt(v) : v;
-    }
-}
-
 
 // K2: exclusive scan of the tile aggregates by one workgroup
 template <class ALG> __global__ void __launch_bounds__(SB) agg_scan_kernel(typename ALG::A* __restrict__ tile_agg, uint32_t ntiles) {

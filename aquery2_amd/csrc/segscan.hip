@@ -4,33 +4,25 @@
 //
 // The FLAT LAYOUT of a grouping: position offsets[g] + i holds element i of group g's row list vecs[g] (ht_postproc order,
 // server/hasher.h:181-198: descending row id inside a group).  aqg_grouped_flatten brings a column into that layout with the
-// value-carrying radix passes of postproc.hip (no row ids, no gather); a bitmap of group starts (`heads`) then makes every kernel of
+// value-carrying radix passes of postproc.hip (no row ids, no gather); a bitmap of group starts (`heads`) then makes every scan of
 // scan.hip segmented:
 //   prefix scans (sums / avgs / mins / maxs / vars / stddevs): reduce-then-scan over 2048-position tiles with the carry
 //       {value, last group start, groups so far} -- a group start resets the value;
-//   windows (sumw / avgw, minw / maxw): tile + halo in LDS as in scan.hip, every window clamped at its group's start
-//       (no carry between tiles: a window never reaches back further than the halo); varw / stddevw: two passes over windows of up
-//       to 64 positions, longer ones from a segmented prefix of moments about the group's first element (any w);
+//   windows (sumw / avgw, minw / maxw): the kernels of scan_window.hpp in their by_group form -- tile + halo in LDS, every window
+//       clamped at its group's start (no carry between tiles: a window never reaches back further than the halo); varw / stddevw:
+//       two passes over windows of up to 64 positions, longer ones from a segmented prefix of moments about the group's first element (any w);
 //   shifts (deltas / prev / aggnext / ratiow): neighbour loads guarded by the start bits.
 // Integer results are exact; floating sums follow the tile order (tolerance as for the whole-column scans).
 // HBM-bound: sizeof(T) + sizeof(out) bytes per row for the scan proper, 12 (one radix pass, <= 256 groups) to 20 x passes for flatten.
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
 #include "scan_dev.hpp"
+#include "scan_window.hpp"
 #include "groupby_handle.hpp"
 
 namespace {
 using namespace aqgscan;
 
-// ---- the carry of a segmented scan -------------------------------------------------------------------------------------------
-// v: fold of the values behind the last group start of the range (of the whole range when it has none); s: position + 1 of that
-// start (0: none); c: group starts in the range
-template <class A> struct SegCarry { A v; uint32_t s; uint32_t c; };
-template <class ALG> struct seg_alg {
-    using A = SegCarry<typename ALG::A>;
-    __device__ static A identity() { A r; r.v = ALG::identity(); r.s = 0; r.c = 0; return r; }
-    __device__ static A op(A a, A b) { A r; r.s = b.s ? b.s : a.s; r.c = a.c + b.c; r.v = b.s ? b.v : ALG::op(a.v, b.v); return r; }
-};
 struct ipair { int64_t s, q; };
 // sum and sum of squares of a group for var / stddev (aggregations.h:332-348): exact for integer columns of up to four bytes -- x * x in the
 // C++ type of the operands, like the reference's `arr[i] * arr[i]` -- and in double for floating columns (the square in the column's type)
@@ -67,22 +59,6 @@ __global__ void __launch_bounds__(256) heads_kernel(const uint32_t* __restrict__
         if (shorts && g < G && counts[g] <= short_w) atomicOr(&shorts[p >> 5], 1u << (p & 31));
     }
 }
-__device__ inline bool head_bit(const uint32_t* __restrict__ heads, uint32_t p) { return (heads[p >> 5] >> (p & 31)) & 1u; }
-// number of predecessors of position p inside its group, capped at maxd (walks the bitmap backwards; position 0 always starts a group)
-__device__ inline uint32_t dist_to_head(const uint32_t* __restrict__ heads, uint32_t p, uint32_t maxd) {
-    uint32_t wi = p >> 5;
-    const uint32_t b = p & 31;
-    uint32_t m = heads[wi] & (0xFFFFFFFFu >> (31 - b));
-    if (m) { const uint32_t d = b - (31 - __clz((int)m)); return d < maxd ? d : maxd; }
-    uint32_t d = b + 1;
-    while (d <= maxd && wi > 0) {
-        m = heads[--wi];
-        if (m) { d += __clz((int)m); return d < maxd ? d : maxd; }
-        d += 32;
-    }
-    return maxd;
-}
-
 // ---- prefix family: K1 tile carries, K2 launch_agg_scan<seg_alg>, K3 results ----------------------------------------------------------
 template <class T, class ALG>
 __global__ void __launch_bounds__(SB) seg_tile_reduce_kernel(const T* __restrict__ x, uint32_t n, const uint8_t* __restrict__ heads8,
@@ -261,260 +237,6 @@ __global__ void __launch_bounds__(SB) seg_shift4_kernel(const T* __restrict__ x,
     }
 }
 
-// ---- sliding sums (sumw / avgw): window_sum_kernel of scan.hip with every window clamped at its group's start ----------
-template <class T, int MODE>
-__global__ void __launch_bounds__(SB) seg_window_sum_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, const uint8_t* __restrict__ heads8, void* __restrict__ out) {
-    using ALG = sum_alg<T>;
-    using A = typename ALG::A;
-    using MX = max_alg<uint32_t>;
-    // Integer sums wrap, so one prefix over the whole extended tile serves every group.  A floating prefix does not: the difference of
-    // two prefixes carries the rounding of everything in front of the window, other groups' rows included (a group of ones behind a
-    // group of 1e30s came out as noise).  Floating columns restart the prefix at every group start (seg_alg).
-    constexpr bool SEG = std::is_floating_point_v<T>;
-    using SA = seg_alg<ALG>;
-    using C = typename SA::A;
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    __shared__ A lds_w[8];
-    __shared__ C lds_c[SEG ? 8 : 1];
-    __shared__ uint32_t lds_m[8];
-    const uint32_t tile_start = blockIdx.x * TS, tile_end = tile_start + TS < n ? tile_start + TS : n;
-    const uint32_t H = (w - 1 + IT - 1) / IT * IT;                // LDS position p <-> row tile_start - H + p
-    const uint32_t L = H + TS, nblk = L / IT;
-    A* S = reinterpret_cast<A*>(smem_raw);
-    uint32_t* LH = reinterpret_cast<uint32_t*>(S + L);            // per block of IT positions: {position + 1 of the last group start BEFORE the block (0: none in this tile), the block's start bits : 8}
-    A carry = ALG::identity();
-    C carry_c = SA::identity();
-    uint32_t carry_m = 0;
-    for (uint32_t blk0 = 0; blk0 < nblk; blk0 += SB) {
-        const uint32_t blk = blk0 + threadIdx.x;
-        const int64_t g0 = (int64_t)tile_start - (int64_t)H + (int64_t)blk * IT;
-        T v[IT];
-        if (blk < nblk && g0 >= 0 && g0 + IT <= (int64_t)n && (((uintptr_t)(x + g0)) & (sizeof(T) * IT > 16 ? 15 : sizeof(T) * IT - 1)) == 0) {
-            pack<T, IT> pk = *reinterpret_cast<const pack<T, IT>*>(x + g0);
-#pragma unroll
-            for (int j = 0; j < IT; ++j) v[j] = pk.v[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < IT; ++j) { const int64_t g = g0 + j; v[j] = (blk < nblk && g >= 0 && g < (int64_t)n) ? x[g] : (T)0; }
-        }
-        const uint32_t hb = (blk < nblk && g0 >= 0 && g0 < (int64_t)n) ? heads8[g0 >> 3] : 0u;
-        const uint32_t lh = hb ? blk * IT + (31 - __clz((int)hb)) + 1 : 0u;
-        A loc[IT];
-        A a = ALG::identity();
-        A excl;
-        if constexpr (SEG) {
-            C ac = SA::identity();
-#pragma unroll
-            for (int j = 0; j < IT; ++j) {
-                if ((hb >> j) & 1u) { ac.v = ALG::identity(); ac.s = 1; ++ac.c; }
-                ac.v = ALG::op(ac.v, ALG::lift(v[j]));
-                loc[j] = ac.v;
-            }
-            C totc;
-            const C ec = SA::op(carry_c, block_scan_excl<SA>(ac, lds_c, totc));
-            excl = ec.v;                                            // what the group that reaches into this block has summed before it
-            carry_c = SA::op(carry_c, totc);
-        } else {
-#pragma unroll
-            for (int j = 0; j < IT; ++j) { a = ALG::op(a, ALG::lift(v[j])); loc[j] = a; }
-            A tot;
-            excl = ALG::op(carry, block_scan_excl<ALG>(a, lds_w, tot));
-            carry = ALG::op(carry, tot);
-        }
-        uint32_t totm;
-        const uint32_t before = MX::op(carry_m, block_scan_excl<MX>(lh, lds_m, totm));
-        if (blk < nblk) {
-#pragma unroll
-            for (int j = 0; j < IT; ++j) S[blk * IT + j] = (SEG && (hb & ((2u << j) - 1u))) ? loc[j] : ALG::op(excl, loc[j]);   // behind a start inside the block: no carry-in
-            LH[blk] = (before << 8) | hb;
-        }
-        carry_m = MX::op(carry_m, totm);
-    }
-    __syncthreads();
-    for (uint32_t i = tile_start + threadIdx.x; i < tile_end; i += SB) {
-        const uint32_t idx = i - tile_start + H, blk = idx >> 3, j = idx & 7;
-        const uint32_t lhb = LH[blk], m = lhb & ((2u << j) - 1u);
-        const uint32_t st = m ? blk * IT + (31 - __clz((int)m)) + 1 : (lhb >> 8);  // position + 1 of the group's start (0: further back than the halo)
-        uint32_t lower = idx + 1 - w;                             // idx >= H >= w - 1
-        if (st && st - 1 > lower) lower = st - 1;
-        const uint32_t len = idx - lower + 1;
-        A s = lower ? ALG::sub(S[idx], S[lower - 1]) : S[idx];
-        if constexpr (SEG) { if (st && st - 1 == lower) s = S[idx]; }    // the window starts where the group does: the restarted prefix is the sum
-        if constexpr (MODE == 0) {
-            if constexpr (std::is_floating_point_v<T>) static_cast<double*>(out)[i] = s;
-            else static_cast<aqg_i128*>(out)[i] = ALG::to_i128(s);
-        } else {
-            static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
-        }
-    }
-}
-// floating inputs, short windows: add the window's elements directly (oldest first), as window_direct_kernel of scan.hip
-template <class T, int MODE>
-__global__ void __launch_bounds__(SB) seg_window_direct_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, const uint32_t* __restrict__ heads, double* __restrict__ out) {
-    uint32_t lo, hi;
-    wg_span(n, lo, hi, 256);
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        const uint32_t len = dist_to_head(heads, i, w - 1) + 1;
-        double s = 0;
-        for (uint32_t j = i + 1 - len; j <= i; ++j) s += (double)x[j];
-        out[i] = MODE == 0 ? s : s / (double)len;
-    }
-}
-// varw / stddevw, windows of up to VAR_DIRECT_MAX_W: var_short_tile with every window clamped at its group's start
-template <class T, bool SD, int RW>
-__global__ void __launch_bounds__(SB) seg_var_short_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, const uint32_t* __restrict__ heads, double* __restrict__ out) {
-    __shared__ T L[TS + VAR_DIRECT_MAX_W];
-    var_short_tile<T, SD, RW>(x, n, w, [&](uint32_t p) { return dist_to_head(heads, p, w - 1) + 1; }, L, out);
-}
-// windows wider than the LDS halo: a segmented inclusive prefix S (SW_RAW) and the distance D of every position to its group's start
-template <class T, int MODE>
-__global__ void __launch_bounds__(SB) seg_prefix_diff_kernel(const typename sum_alg<T>::A* __restrict__ S, const uint32_t* __restrict__ D, uint32_t n, uint32_t w, void* __restrict__ out) {
-    using ALG = sum_alg<T>;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t d = D[i], len = d + 1 < w ? d + 1 : w;
-        auto s = len == d + 1 ? S[i] : ALG::sub(S[i], S[i - len]);
-        if constexpr (MODE == 0) {
-            if constexpr (std::is_floating_point_v<T>) static_cast<double*>(out)[i] = s; else static_cast<aqg_i128*>(out)[i] = ALG::to_i128(s);
-        } else static_cast<double*>(out)[i] = ALG::to_double(s) / (double)len;
-    }
-}
-
-// ---- sliding min / max: window_minmax_kernel of scan.hip (doubling, eight positions per lane), a level taken only where the position
-// 2^k back still belongs to the group: DS[p] = predecessors of p inside its group (capped) ----------------------------------------------
-template <class T, bool IS_MAX>
-__global__ void __launch_bounds__(SB) seg_window_minmax_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, const uint8_t* __restrict__ heads8, T* __restrict__ out) {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    constexpr int E = 8;
-    struct alignas(E * sizeof(T) > 16 ? 16 : E * sizeof(T)) blk_t { T v[E]; };
-    struct alignas(16) dblk_t { uint16_t d[E]; };
-    __shared__ uint32_t lds_m[8];
-    using MX = max_alg<uint32_t>;
-    const uint32_t tile_start = blockIdx.x * TS;
-    const uint32_t H = (w - 1 + E - 1) / E * E;
-    const uint32_t L = H + TS, nblk = L / E;
-    T* M0 = reinterpret_cast<T*>(smem_raw);
-    T* M1 = M0 + L;
-    uint16_t* DS = reinterpret_cast<uint16_t*>(M1 + L);
-    T ident;
-    if constexpr (std::is_floating_point_v<T>) ident = IS_MAX ? -(T)INFINITY : (T)INFINITY;
-    else ident = IS_MAX ? dlimits<T>::min() : dlimits<T>::max();
-    auto better = [](T a, T b) { if constexpr (IS_MAX) return b > a ? b : a; else return b < a ? b : a; };
-    for (uint32_t p = threadIdx.x; p < H; p += SB) {
-        const int64_t g = (int64_t)tile_start - (int64_t)H + p;
-        M0[p] = g >= 0 ? x[g] : ident;
-    }
-    {
-        const uint32_t g0 = tile_start + threadIdx.x * E;
-        blk_t b;
-        if (g0 + E <= n && (reinterpret_cast<uintptr_t>(x + g0) & (alignof(blk_t) - 1)) == 0) b = *reinterpret_cast<const blk_t*>(x + g0);
-        else {
-#pragma unroll
-            for (int q = 0; q < E; ++q) b.v[q] = g0 + q < n ? x[g0 + q] : ident;
-        }
-        *reinterpret_cast<blk_t*>(M0 + H + threadIdx.x * E) = b;
-    }
-    uint32_t carry_m = 0;
-    for (uint32_t blk0 = 0; blk0 < nblk; blk0 += SB) {             // distances to the group starts (a start further back than the halo: "far")
-        const uint32_t blk = blk0 + threadIdx.x;
-        const int64_t g0 = (int64_t)tile_start - (int64_t)H + (int64_t)blk * E;
-        const uint32_t hb = (blk < nblk && g0 >= 0 && g0 < (int64_t)n) ? heads8[g0 >> 3] : 0u;
-        const uint32_t lh = hb ? blk * E + (31 - __clz((int)hb)) + 1 : 0u;
-        uint32_t totm;
-        uint32_t cur = MX::op(carry_m, block_scan_excl<MX>(lh, lds_m, totm));
-        if (blk < nblk) {
-            dblk_t dd;
-#pragma unroll
-            for (int q = 0; q < E; ++q) {
-                if ((hb >> q) & 1) cur = blk * E + q + 1;
-                const uint32_t dist = cur ? blk * E + q - (cur - 1) : 0xFFFFu;
-                dd.d[q] = (uint16_t)(dist < 0xFFFFu ? dist : 0xFFFFu);
-            }
-            *reinterpret_cast<dblk_t*>(DS + blk * E) = dd;
-        }
-        carry_m = MX::op(carry_m, totm);
-    }
-    __syncthreads();
-    uint32_t K = 0;
-    while ((2u << K) <= w) ++K;                                    // 2^K <= w < 2^(K+1)
-    const uint32_t KA = K < 3 ? K : 3;
-    T* cur = M0; T* nxt = M1;
-    if (KA) {
-        for (uint32_t blk = threadIdx.x; blk < nblk; blk += SB) {
-            T a[2 * E];
-            uint32_t dist[2 * E];
-            const blk_t own = *reinterpret_cast<const blk_t*>(cur + blk * E);
-            const dblk_t downd = *reinterpret_cast<const dblk_t*>(DS + blk * E);
-            blk_t prev;
-            dblk_t dprev;
-            if (blk) { prev = *reinterpret_cast<const blk_t*>(cur + (blk - 1) * E); dprev = *reinterpret_cast<const dblk_t*>(DS + (blk - 1) * E); }
-#pragma unroll
-            for (int q = 0; q < E; ++q) { a[q] = blk ? prev.v[q] : ident; a[E + q] = own.v[q]; dist[q] = blk ? dprev.d[q] : 0u; dist[E + q] = downd.d[q]; }
-#pragma unroll
-            for (uint32_t k = 0; k < 3; ++k) {
-                if (k < KA) {
-                    const int d = 1 << k;
-#pragma unroll
-                    for (int j = 2 * E - 1; j >= d; --j) if (dist[j] >= (uint32_t)d) a[j] = better(a[j], a[j - d]);
-                }
-            }
-            blk_t o;
-#pragma unroll
-            for (int q = 0; q < E; ++q) o.v[q] = a[E + q];
-            *reinterpret_cast<blk_t*>(nxt + blk * E) = o;
-        }
-        __syncthreads();
-        T* t = cur; cur = nxt; nxt = t;
-    }
-    for (uint32_t k = KA; k < K; ++k) {
-        const uint32_t db = (1u << k) / E, dk = 1u << k;
-        for (uint32_t blk = threadIdx.x; blk < nblk; blk += SB) {
-            blk_t a = *reinterpret_cast<const blk_t*>(cur + blk * E);
-            if (blk >= db) {
-                const blk_t b = *reinterpret_cast<const blk_t*>(cur + (blk - db) * E);
-                const dblk_t dd = *reinterpret_cast<const dblk_t*>(DS + blk * E);
-#pragma unroll
-                for (int q = 0; q < E; ++q) if (dd.d[q] >= dk) a.v[q] = better(a.v[q], b.v[q]);
-            }
-            *reinterpret_cast<blk_t*>(nxt + blk * E) = a;
-        }
-        __syncthreads();
-        T* t = cur; cur = nxt; nxt = t;
-    }
-    const uint32_t off = w - (1u << K);
-    const uint32_t p0 = H + threadIdx.x * E, g0 = tile_start + threadIdx.x * E;
-    if (g0 < n) {
-        blk_t a = *reinterpret_cast<const blk_t*>(cur + p0);
-        if (off) {
-            const dblk_t dd = *reinterpret_cast<const dblk_t*>(DS + p0);
-#pragma unroll
-            for (int q = 0; q < E; ++q) if (dd.d[q] >= off) a.v[q] = better(a.v[q], cur[p0 + q - off]);
-        }
-        if (g0 + E <= n && (reinterpret_cast<uintptr_t>(out + g0) & (alignof(blk_t) - 1)) == 0) *reinterpret_cast<blk_t*>(out + g0) = a;
-        else {
-#pragma unroll
-            for (int q = 0; q < E; ++q) if (g0 + q < n) out[g0 + q] = a.v[q];
-        }
-    }
-}
-// windows wider than the LDS halo: doubling passes through HBM guarded by the distances D
-template <class T, bool IS_MAX>
-__global__ void __launch_bounds__(SB) seg_doubling_pass_kernel(const T* __restrict__ src, T* __restrict__ dst, const uint32_t* __restrict__ D, uint32_t n, uint32_t d) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        T a = src[i];
-        if (D[i] >= d) { T b = src[i - d]; if constexpr (IS_MAX) a = b > a ? b : a; else a = b < a ? b : a; }
-        dst[i] = a;
-    }
-}
-template <class T, bool IS_MAX>
-__global__ void __launch_bounds__(SB) seg_doubling_final_kernel(const T* __restrict__ m, T* __restrict__ out, const uint32_t* __restrict__ D, uint32_t n, uint32_t w, uint32_t span) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint32_t len = D[i] + 1 < w ? D[i] + 1 : w;
-        T a = m[i];
-        if (len > span) { T b = m[i - (len - span)]; if constexpr (IS_MAX) a = b > a ? b : a; else a = b < a ? b : a; }
-        out[i] = a;
-    }
-}
-
 __global__ void __launch_bounds__(256) ends_kernel(const uint32_t* __restrict__ off, uint32_t G, uint32_t* __restrict__ last_pos) {
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < G; g += gridDim.x * blockDim.x) last_pos[g] = off[g + 1] - 1;
 }
@@ -579,6 +301,22 @@ int seg_prefix(aqg_ctx* ctx, aqg_groupby* g, const T* x, uint32_t n, void* out) 
 }
 int dist_column(aqg_ctx* ctx, aqg_groupby* g, uint32_t n, uint32_t* D) { return seg_prefix<uint8_t, none_alg, SW_DIST>(ctx, g, nullptr, n, D); }
 
+// what window_scan (scan_window.hpp) asks of a layout, for the flat layout of a grouping
+template <class T> struct group_windows {
+    using seg_t = by_group;
+    aqg_ctx* ctx; aqg_groupby* g; const T* x; uint32_t n; unsigned row_grid;
+    by_group seg() const { return {g->flat_heads, nullptr}; }
+    int reserve(size_t) { return AQG_OK; }                           // the caller sized the workspace (scan_ws_bytes) and it is not reset in here
+    int raw_prefix(typename sum_alg<T>::A* S) { return seg_prefix<T, sum_alg<T>, SW_RAW>(ctx, g, x, n, S); }
+    int moments(dpair* P) { return seg_prefix<T, mom_alg<T>, SW_MOM>(ctx, g, x, n, P); }
+    int distances(by_group& s) {
+        uint32_t* D;
+        AQG_TRY(aqg_ws_get(ctx, n, &D));
+        s.D = D;
+        return dist_column(ctx, g, n, D);
+    }
+};
+
 size_t scan_ws_bytes(int op, int t, uint32_t n, uint32_t w) {
     size_t need = carry_ws_bytes(n) * 2 + 65536;
     const size_t esz = aqg_dtype_size(t);
@@ -595,14 +333,12 @@ size_t scan_ws_bytes(int op, int t, uint32_t n, uint32_t w) {
 // the scan of a column already in the flat layout (workspace sized by scan_ws_bytes and not reset in here)
 int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint32_t w, void* out) {
     const uint32_t n = g->n;
-    const uint8_t* heads8 = reinterpret_cast<const uint8_t*>(g->flat_heads);
     const uint32_t* heads = g->flat_heads;
     if (op == AQG_SCAN_RATIOW && w >= 2) AQG_TRY(ensure_short(ctx, g, w));
     const uint32_t* shorts = (op == AQG_SCAN_RATIOW && w >= 2) ? g->flat_short : nullptr;
     return aqg_dispatch_num(t, [&](auto tt) -> int {
         using T = typename decltype(tt)::type;
         const T* x = static_cast<const T*>(xv);
-        const uint32_t ntiles = aqg_ceil_div(n, TS);
         const unsigned egrid = aqg_grid(ctx, n, SB, 4, 16);
         auto shift = [&](auto kern, const char* what) -> int {
             aqg_kernel_timer_begin(ctx);
@@ -610,6 +346,7 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
             aqg_kernel_timer_end(ctx);
             return aqg_check_launch(ctx, what);
         };
+        group_windows<T> grp{ctx, g, x, n, egrid};
         const bool al16 = ((reinterpret_cast<uintptr_t>(xv) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && n >= 4;
         auto shift4 = [&](auto kern, const char* what) -> int {
             aqg_kernel_timer_begin(ctx);
@@ -624,99 +361,17 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
         case AQG_SCAN_MAXS: return seg_prefix<T, max_alg<T>, SW_MAXS>(ctx, g, x, n, out);
         case AQG_SCAN_VARS: return seg_prefix<T, mom_alg<T>, SW_VARS>(ctx, g, x, n, out);
         case AQG_SCAN_STDDEVS: return seg_prefix<T, mom_alg<T>, SW_STDDEVS>(ctx, g, x, n, out);
-        case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: {
-            const bool sd = op == AQG_SCAN_STDDEVW;
-            const uint32_t ww = w > n ? n : w;
-            if (ww <= VAR_DIRECT_MAX_W) {
-                auto go = [&](auto kern) -> int {
-                    aqg_kernel_timer_begin(ctx);
-                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, ww, heads, static_cast<double*>(out));
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "seg_var_short_kernel");
-                };
-                if (ww <= (uint32_t)VAR_REG_W) return sd ? go(&seg_var_short_kernel<T, true, VAR_REG_W>) : go(&seg_var_short_kernel<T, false, VAR_REG_W>);
-                return sd ? go(&seg_var_short_kernel<T, true, 0>) : go(&seg_var_short_kernel<T, false, 0>);
-            }
-            dpair* P; uint32_t* D;
-            AQG_TRY(aqg_ws_get(ctx, n, &P));
-            AQG_TRY(aqg_ws_get(ctx, n, &D));
-            AQG_TRY((seg_prefix<T, mom_alg<T>, SW_MOM>(ctx, g, x, n, P)));
-            AQG_TRY(dist_column(ctx, g, n, D));
-            if (sd) hipLaunchKernelGGL((var_prefix_diff_kernel<true>), dim3(egrid), dim3(SB), 0, ctx->stream, P, D, n, ww, static_cast<double*>(out));
-            else hipLaunchKernelGGL((var_prefix_diff_kernel<false>), dim3(egrid), dim3(SB), 0, ctx->stream, P, D, n, ww, static_cast<double*>(out));
-            return aqg_check_launch(ctx, "wide window variance (grouped)");
-        }
+        case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: case AQG_SCAN_SUMW: case AQG_SCAN_AVGW:
+            return window_scan(ctx, grp, op, x, n, w > n ? n : w, out);                 // (a window is clamped by its group anyway)
         case AQG_SCAN_DELTAS: return al16 ? shift4(&seg_shift4_kernel<T, AQG_SCAN_DELTAS>, "deltas (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_DELTAS>, "deltas (grouped)");
         case AQG_SCAN_PREV: return al16 ? shift4(&seg_shift4_kernel<T, AQG_SCAN_PREV>, "prev (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_PREV>, "prev (grouped)");
         case AQG_SCAN_NEXT: return al16 ? shift4(&seg_shift4_kernel<T, AQG_SCAN_NEXT>, "aggnext (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_NEXT>, "aggnext (grouped)");
         case AQG_SCAN_RATIOW: return (al16 && w == 1) ? shift4(&seg_shift4_kernel<T, AQG_SCAN_RATIOW>, "ratios (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_RATIOW>, "ratiow (grouped)");
-        case AQG_SCAN_SUMW: case AQG_SCAN_AVGW: {
-            using A = typename sum_alg<T>::A;
-            const uint32_t ww = w > n ? n : w;                                          // (a window is clamped by its group anyway)
-            if constexpr (std::is_floating_point_v<T>) {
-                if (ww <= 64) {
-                    aqg_kernel_timer_begin(ctx);
-                    if (op == AQG_SCAN_SUMW) hipLaunchKernelGGL((seg_window_direct_kernel<T, 0>), dim3(egrid), dim3(SB), 0, ctx->stream, x, n, ww, heads, static_cast<double*>(out));
-                    else hipLaunchKernelGGL((seg_window_direct_kernel<T, 1>), dim3(egrid), dim3(SB), 0, ctx->stream, x, n, ww, heads, static_cast<double*>(out));
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "seg_window_direct_kernel");
-                }
-            }
-            const size_t ext = (size_t)TS + (ww - 1 + IT - 1) / IT * IT;
-            const size_t lds = ext * sizeof(A) + ext / IT * 4 + 16;
-            if (lds <= HALO_MAX_BYTES) {
-                auto go = [&](auto kern) -> int {
-                    AQG_TRY(aqg_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-                    aqg_kernel_timer_begin(ctx);
-                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), lds, ctx->stream, x, n, ww, heads8, out);
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "seg_window_sum_kernel");
-                };
-                return op == AQG_SCAN_SUMW ? go(&seg_window_sum_kernel<T, 0>) : go(&seg_window_sum_kernel<T, 1>);
-            }
-            A* S; uint32_t* D;
-            AQG_TRY(aqg_ws_get(ctx, n, &S));
-            AQG_TRY(aqg_ws_get(ctx, n, &D));
-            AQG_TRY((seg_prefix<T, sum_alg<T>, SW_RAW>(ctx, g, x, n, S)));
-            AQG_TRY(dist_column(ctx, g, n, D));
-            if (op == AQG_SCAN_SUMW) hipLaunchKernelGGL((seg_prefix_diff_kernel<T, 0>), dim3(egrid), dim3(SB), 0, ctx->stream, S, D, n, ww, out);
-            else hipLaunchKernelGGL((seg_prefix_diff_kernel<T, 1>), dim3(egrid), dim3(SB), 0, ctx->stream, S, D, n, ww, out);
-            return aqg_check_launch(ctx, "wide window sum (grouped)");
-        }
         case AQG_SCAN_MINW: case AQG_SCAN_MAXW: {
             const bool is_max = op == AQG_SCAN_MAXW;
             // the deque never expires anything when w == 0 or w >= n: the running min / max of the group (no seed)
             if (w == 0 || w >= n) return is_max ? seg_prefix<T, max_alg<T>, SW_MAXP>(ctx, g, x, n, out) : seg_prefix<T, min_alg<T>, SW_MINP>(ctx, g, x, n, out);
-            const size_t ext = (size_t)TS + (w - 1 + 7) / 8 * 8;
-            const size_t lds = ext * sizeof(T) * 2 + ext * 2 + 16;
-            if (lds <= HALO_MAX_BYTES) {
-                auto go = [&](auto kern) -> int {
-                    AQG_TRY(aqg_allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-                    aqg_kernel_timer_begin(ctx);
-                    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(SB), lds, ctx->stream, x, n, w, heads8, static_cast<T*>(out));
-                    aqg_kernel_timer_end(ctx);
-                    return aqg_check_launch(ctx, "seg_window_minmax_kernel");
-                };
-                return is_max ? go(&seg_window_minmax_kernel<T, true>) : go(&seg_window_minmax_kernel<T, false>);
-            }
-            T *b0, *b1; uint32_t* D;
-            AQG_TRY(aqg_ws_get(ctx, n, &b0));
-            AQG_TRY(aqg_ws_get(ctx, n, &b1));
-            AQG_TRY(aqg_ws_get(ctx, n, &D));
-            AQG_TRY(dist_column(ctx, g, n, D));
-            uint32_t K = 0;
-            while ((2u << K) <= w && K < 31) ++K;
-            const T* src = x;
-            T* dst = b0;
-            for (uint32_t k = 0; k < K; ++k) {
-                if (is_max) hipLaunchKernelGGL((seg_doubling_pass_kernel<T, true>), dim3(egrid), dim3(SB), 0, ctx->stream, src, dst, D, n, 1u << k);
-                else hipLaunchKernelGGL((seg_doubling_pass_kernel<T, false>), dim3(egrid), dim3(SB), 0, ctx->stream, src, dst, D, n, 1u << k);
-                src = dst;
-                dst = dst == b0 ? b1 : b0;
-            }
-            if (is_max) hipLaunchKernelGGL((seg_doubling_final_kernel<T, true>), dim3(egrid), dim3(SB), 0, ctx->stream, src, static_cast<T*>(out), D, n, w, 1u << K);
-            else hipLaunchKernelGGL((seg_doubling_final_kernel<T, false>), dim3(egrid), dim3(SB), 0, ctx->stream, src, static_cast<T*>(out), D, n, w, 1u << K);
-            return aqg_check_launch(ctx, "wide window min/max (grouped)");
+            return window_scan(ctx, grp, op, x, n, w, out);
         }
         }
         return AQG_ERR_ARG;

@@ -27,7 +27,7 @@ What is left out, and why -- nothing else is skipped, and nothing is skipped dep
                                                     the pairs are run with the expression's own C++ type as result type instead
   sumw / avgw with w == 0                           DESIGN.md 2: "`sumw/avgw` with `w == 0` read `ret[-1]` (rejected with `AQG_ERR_ARG`)"
   floating sumw / avgw, 64 < w: rounding of the     DESIGN.md 2: "Floating sums: any re-ordered summation is bounded by ..." -- these routes
-  tile + halo (hbm route: of the whole prefix)      take the difference of two prefixes (scan.hip window_sum_kernel: over the 2048-row tile and
+  tile + halo (hbm route: of the whole prefix)      take the difference of two prefixes (scan_window.hpp window_sum_kernel: over the 2048-row tile and
   instead of the window's rows alone                its halo; prefix_diff_kernel: over the column), so that is the summation the bound is about
   NaN in a column of min / max / mins / maxs /      DESIGN.md 2, "NaN and signed zeros": the reference's folds forget what came before a NaN and
   minw / maxw or of the floating sum family         its window sums stay NaN: every output row strictly before the first NaN row is held to the
@@ -398,9 +398,9 @@ TS = 2048                                                    # rows per tile (sc
 HALO_MAX_BYTES = 96 * 1024
 
 
-# The two functions below restate the dispatch of aqg_scan (scan.hip: `case AQG_SCAN_MINW: case AQG_SCAN_MAXW:` -- the ww == n test, the
-# van Herk candidates `for (int cand : {9, 7, 5, 3})` / `{5, 7, 9, 11}`, `lds <= HALO_MAX_BYTES`; `case AQG_SCAN_SUMW: case AQG_SCAN_AVGW:` --
-# `ww <= 64` for floating columns, `lds <= HALO_MAX_BYTES`; scan_dev.hpp: TS, HALO_MAX_BYTES).  A change of those constants has to be made here too:
+# The two functions below restate the dispatch of aqg_scan (scan.hip, `case AQG_SCAN_MINW: case AQG_SCAN_MAXW:` -- the ww == n test and the
+# van Herk candidates `for (int cand : {9, 7, 5, 3})` / `{5, 7, 9, 11}`) and of window_scan (scan_window.hpp: `lds <= HALO_MAX_BYTES` for both
+# families, `ww <= DIRECT_MAX_W` (64) for floating sums; scan_dev.hpp: TS, HALO_MAX_BYTES).  A change of those constants has to be made here too:
 # the names only label the test ids and choose window_reference's span, every window length is compared with the oracle whatever its route.
 def minmax_route(dt, n, w, aligned):
     """the route aqg_scan takes for minw / maxw (scan.hip, case AQG_SCAN_MINW)"""
@@ -469,7 +469,7 @@ def inf_runs_column(dt, n, seed, sign=1.0):
 def window_reference(x, w, route):
     """(sum over the last min(i + 1, w) rows, bound) computed over exactly the rows a route of aqg_scan adds, in double:
     direct -- the window's rows, oldest first; bound w 2^-52 sum|x| over the window.
-    lds    -- the difference of two prefixes over the row's 2048-row tile and its halo of w - 1 rows rounded up to 8 (scan.hip window_sum_kernel);
+    lds    -- the difference of two prefixes over the row's 2048-row tile and its halo of w - 1 rows rounded up to 8 (scan_window.hpp window_sum_kernel);
               bound (halo + 2048) 2^-52 sum|x| over tile and halo.
     Rows whose span holds an infinity come out non-finite here and are left to the comparison with the oracle."""
     from numpy.lib.stride_tricks import sliding_window_view as swv
@@ -725,7 +725,7 @@ def test_grouped_scan_at_the_extremes(gpu, oracle):
             got, want = both(name, z, w)
             assert np.all(np.abs(got - want) <= pos * 2.0 ** -52 * absz), (ex.nm(dt), name, w)      # the oracle's recurrence has touched the group's earlier rows
         # a window's rows are the window's: against the sum of the rows the route adds, per group -- w = 5 the window itself (direct route), w = 100 the
-        # group's rows inside the tile and its halo (seg_window_sum_kernel restarts its prefix at every group start): at most 2048 + 104 of them
+        # group's rows inside the tile and its halo (window_sum_kernel over by_group restarts its prefix at every group start): at most 2048 + 104 of them
         trail = lambda a, k: np.lib.stride_tricks.sliding_window_view(np.concatenate([np.zeros(k - 1), a]), k).sum(axis=1)
         for w, span in ((5, 5), (100, TS + 104)):
             got = gpu.grouped_scan(gb, ck.SCAN_SUMW, z, w)

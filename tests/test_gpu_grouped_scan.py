@@ -12,6 +12,7 @@ import pytest
 import checker as ck
 import exact_moments as em
 import golden_util as gu
+import window_checks as wc
 from test_gpu_basic import rand
 
 pytestmark = pytest.mark.gpu
@@ -91,15 +92,9 @@ def test_grouped_scan_random_shapes(gpu, oracle, seed):
 
     def check_var(name, w, got):
         """the variance contract against the exact values (tests/exact_moments.py), and the oracle's composition where it is cheap"""
-        T = exact.var(None if name in ("vars", "stddevs") else w)
-        sd = name.startswith("stddev")
-        exact.check(got, T, None if name in ("vars", "stddevs") else w, sd=sd, what=f"{seed} {name} {np.dtype(dt)} w={w} n={n} G={G}")
-        if n * min(max(w, 1), n) <= 3_000_000:
-            op = ck.SCAN_NAMES[name]
-            want = compose(ogb, x, lambda v: oracle.scan(op, v, w), np.float64)
-            b, _ = em.bound(xf, T, None if name in ("vars", "stddevs") else w, ogb["offsets"])
-            tol = np.sqrt(b) if sd else b
-            assert np.all(np.abs(got - want) <= 2 * tol + 1e-9 * np.abs(want)), (seed, name, dt, w, n, G)
+        op = ck.SCAN_NAMES[name]
+        want = compose(ogb, x, lambda v: oracle.scan(op, v, w), np.float64) if n * min(max(w, 1), n) <= 3_000_000 else None
+        wc.variance(exact, name, w, got, f"{seed} {name} {np.dtype(dt)} w={w} n={n} G={G}", want)
 
     for name in rng.choice(SCANS, 3, replace=False):
         op = ck.SCAN_NAMES[str(name)]
@@ -119,12 +114,7 @@ def test_grouped_scan_random_shapes(gpu, oracle, seed):
             continue                                          # the reference wraps arr[i] - arr[i-w] for unsigned 4/8-byte inputs
         want = compose(ogb, x, lambda v: oracle.scan(op, v, w), ck.TAG2NP[oracle.scan_out_dtype(op, ck.tag_of(x))])
         got = gpu.grouped_scan(gb, op, x, w)
-        if name in ("minw", "maxw") or (name == "sumw" and not fp) or name == "ratiow":
-            assert gu.same_bits(got, want), (seed, name, dt, w, n, G)
-        else:
-            eps_in = float(np.finfo(dt).eps) if fp else 2.0 ** -52
-            bound = 4 * eps_in * float(np.max(absx)) * (pos + 2) + 1e-9
-            assert np.all(np.abs(got.astype(np.float64) - want.astype(np.float64)) <= bound), (seed, name, dt, w, n, G)
+        wc.grouped_window(name, dt, got, want, absx, pos, (seed, name, dt, w, n, G))
     # the variance ops on every seed, in addition to the picks above (their own generator: the draws above stay as they were)
     vrng = np.random.default_rng(int(os.environ.get("AQG_FUZZ_BASE", "9100")) + seed + 1_000_000)
     for name in ("vars", "stddevs"):

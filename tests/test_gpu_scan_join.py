@@ -5,6 +5,7 @@ import pytest
 
 import checker as ck
 import golden_util as gu
+import window_checks as wc
 
 pytestmark = pytest.mark.gpu
 
@@ -32,11 +33,6 @@ def rand(rng, dt, n, small=False):
     return x
 
 
-def ulp_close(a, b, ulps):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.all(np.abs(a - b) <= ulps * np.spacing(np.maximum(np.abs(a), np.abs(b))))
-
-
 @pytest.mark.parametrize("dt", NUM_DTYPES)
 @pytest.mark.parametrize("n", [1, 5, 2048, 2049, 70001])
 def test_scans_exact(gpu, oracle, dt, n):
@@ -61,35 +57,12 @@ def test_scans_sums(gpu, oracle, dt, n):
     (aggregations.h:270-271), so both are compared with the exact rational.  Floating inputs: tree order vs sequential."""
     rng = np.random.default_rng(n * 3 + np.dtype(dt).num)
     x = rand(rng, dt, n)
-    is_int = np.dtype(dt).kind != "f"
     for name in SUM_SCANS:
         for w in (1, 2, 3, 10, 100, 2048, 5000, 100000):
             if name in ("sums", "avgs") and w != 1:
                 continue
             a, b = gpu.scan(ck.SCAN_NAMES[name], x, w), oracle.scan(ck.SCAN_NAMES[name], x, w)
-            if is_int and name in ("sums", "sumw", "avgs"):
-                assert gu.same_bits(a, b), (name, w, dt, n)
-            elif is_int:  # avgw
-                ww = min(w, n)
-                xs = [int(v) for v in x]
-                pref = np.concatenate([[0], np.cumsum(np.array(xs, dtype=object))])
-                idx = np.arange(n)
-                lens = np.minimum(idx + 1, ww)
-                exact = np.array([float((pref[i + 1] - pref[i + 1 - l])) / float(l) for i, l in zip(idx, lens)])
-                assert ulp_close(a, exact, 1), (name, w, dt)                       # device: <= 1 ulp of the exact mean
-                if np.dtype(dt).kind == "u" and np.dtype(dt).itemsize >= 4:
-                    continue   # reference quirk: (arr[i] - arr[i-w]) wraps for unsigned 4/8-byte inputs (aggregations.h:271)
-                drift = 4.0 * np.spacing(float(np.max(np.abs(exact))) + 1.0) * (idx + 2)   # ~2 roundings per step at the largest magnitude
-                assert np.all(np.abs(b - exact) <= drift), (name, w, dt)           # reference: inside its recurrence drift
-                assert np.all(np.abs(a - b) <= drift)
-            else:
-                scale = np.maximum(1.0, np.abs(b.astype(np.float64)))
-                # avgw: the reference subtracts arr[i]-arr[i-w] in T (float32 rounding per step), then drifts
-                eps = float(np.finfo(dt).eps) if name == "avgw" else 2.0 ** -52
-                sabs = float(np.sum(np.abs(x.astype(np.float64))))
-                # any summation order: |err| <= (n-1) u sum|x| (both sides); avgw additionally carries the reference's per-step T rounding
-                tol = 2 * n * 2.0 ** -52 * sabs + (100.0 * eps * float(np.max(np.abs(x))) * (np.arange(n) + 8) if name == "avgw" else 0)
-                assert np.all(np.abs(a.astype(np.float64) - b.astype(np.float64)) <= tol), (name, w, dt)
+            wc.column_sum_scan(name, w, x, a, b)
 
 
 def test_scans_golden(gpu):
