@@ -1,6 +1,7 @@
 // partition1_int.hpp -- what the partition plans (partition1.hip, partition_wide.hip, sorted_tail.hip, partition_assign.hip), the
-// tile scatter they move rows with (tile_scatter.hip) and partition1_agg.hip (the per-partition aggregation kernels and their launchers) share:
-// the key word, the accumulator operand codes, the value-column and packing plans, and the launchers one file offers another.
+// tile scatter they move rows with (tile_scatter.hip) and partition1_agg.hip (the three per-partition aggregation kernels and their launcher) share:
+// the key word, the accumulator operand codes and their one choice on the host (p1_opcode), the value-column and packing plans, and the
+// launchers one file offers another.
 #pragma once
 #include <cmath>
 #include "groupby_dev.hpp"
@@ -34,6 +35,18 @@ __device__ inline uint64_t val_operand_bits(int dt, uint64_t bits, int kind, int
 // loop was VALU- and branch-bound with that switch evaluated per row and accumulator (h2o Q5, 1e9 rows: 9.1 ms for 20 GB).
 enum : int { OPC_ADDI_I32 = 0, OPC_ADDI_U32, OPC_ADDF_F32, OPC_ADDF_F64, OPC_MIN_I32, OPC_MAX_I32, OPC_MIN_U32, OPC_MAX_U32, OPC_MIN_F32, OPC_MAX_F32, OPC_GENERIC };
 struct AggOps { int opc[MAXACC]; };
+// adds_only: for the kernels with straight-line code for the four adds alone (pw_agg_kernel, gid_agg_kernel), whose generic arm
+// takes every other accumulator
+static inline int p1_opcode(int dt, int kind, int square, int part, bool adds_only = false) {
+    int opc = OPC_GENERIC;
+    if (!square && !part) {
+        if (dt == AQG_INT32) opc = kind == ACC_ADD_I ? OPC_ADDI_I32 : kind == ACC_MIN ? OPC_MIN_I32 : kind == ACC_MAX ? OPC_MAX_I32 : OPC_GENERIC;
+        else if (dt == AQG_UINT32) opc = kind == ACC_ADD_I ? OPC_ADDI_U32 : kind == ACC_MIN ? OPC_MIN_U32 : kind == ACC_MAX ? OPC_MAX_U32 : OPC_GENERIC;
+        else if (dt == AQG_FLOAT) opc = kind == ACC_ADD_F ? OPC_ADDF_F32 : kind == ACC_MIN ? OPC_MIN_F32 : kind == ACC_MAX ? OPC_MAX_F32 : OPC_GENERIC;
+        else if (dt == AQG_DOUBLE && kind == ACC_ADD_F) opc = OPC_ADDF_F64;
+    }
+    return adds_only && opc > OPC_ADDF_F64 ? OPC_GENERIC : opc;        // (the adds are the first four codes)
+}
 
 constexpr size_t AGG_LDS = 150 * 1024;
 constexpr uint32_t LF1000 = 500;    // load factor of the key table

@@ -495,15 +495,7 @@ int aqg_partitionw_aggregate(aqg_ctx* ctx, const KeySpec& ks, const AccSpec& as,
     for (int a = 0; a < as.nacc; ++a) {
         if (vc.of_acc[a] >= 0) { in.vcol[a] = from->val[vc.of_acc[a]]; in.vesz[a] = vsrc[vc.of_acc[a]].bytes; }
         else { in.vcol[a] = nullptr; in.vesz[a] = 4; }
-        const int dt = as.dt[a], kind = as.kind[a];
-        int opc = OPC_GENERIC;
-        if (!as.square[a] && !as.part[a]) {
-            if (dt == AQG_INT32 && kind == ACC_ADD_I) opc = OPC_ADDI_I32;
-            else if (dt == AQG_UINT32 && kind == ACC_ADD_I) opc = OPC_ADDI_U32;
-            else if (dt == AQG_FLOAT && kind == ACC_ADD_F) opc = OPC_ADDF_F32;
-            else if (dt == AQG_DOUBLE && kind == ACC_ADD_F) opc = OPC_ADDF_F64;
-        }
-        ops.opc[a] = opc;
+        ops.opc[a] = p1_opcode(as.dt[a], as.kind[a], as.square[a], as.part[a], true);
     }
     const size_t lds = w.lds;
     unsigned per_cu = (unsigned)((160 * 1024) / (lds + 512));
@@ -846,8 +838,7 @@ static int gid_reduce_impl(aqg_ctx* ctx, const uint32_t* gid, const uint32_t* of
     a.gid = gsrc; a.val = vs; a.vdt = t; a.op = op; a.pstart = pstart; a.pfirst = pfirst; a.counts = counts; a.out = out_dev; a.nparts = PP; a.cap = cap;
     a.packed = pk_on; a.idmask = pk_on ? ~kclear : 0xFFFFFFFFu; a.pshift = pk_shift; a.pmin = pk_min;
     a.ntotal = n;
-    a.opc = OPC_GENERIC;
-    if (op == AQG_RED_SUM || op == AQG_RED_AVG) a.opc = t == AQG_INT32 ? OPC_ADDI_I32 : t == AQG_UINT32 ? OPC_ADDI_U32 : t == AQG_FLOAT ? OPC_ADDF_F32 : t == AQG_DOUBLE ? OPC_ADDF_F64 : OPC_GENERIC;
+    a.opc = op == AQG_RED_SUM || op == AQG_RED_AVG ? p1_opcode(t, vclass(t) == VC_F ? ACC_ADD_F : ACC_ADD_I, 0, 0, true) : OPC_GENERIC;
     if (n < 1024u * 8u) return AQG_ERR_DTYPE;                                 // (the kernel prefetches whole steps of 8192 rows; inputs this small never come here)
     const size_t lds = (size_t)cap * 8 * (two ? 2 : 1);
     auto launch = [&](auto kern) -> int {
