@@ -25,6 +25,7 @@ TAG2NP = {
 NP2TAG = {v: k for k, v in TAG2NP.items() if k != BOOL}
 NP2TAG[np.dtype(np.bool_)] = BOOL
 VEC_VEC, VEC_SCALAR, SCALAR_VEC = 0, 1, 2
+LAYOUT_ROW, LAYOUT_FLAT = 0, 1                                 # aqg_grouped_ewise: the layout of the column operand
 ORDER_ASC, ORDER_DESC, ORDER_NEG = 0, 1, 2
 SEL_LOWER, SEL_UPPER = 0, 1                                   # aqg_median: rank (c-1)/2 resp. c/2 of the c rows in ascending order
 ROUTE_SMALL, ROUTE_GROUP, ROUTE_SPLIT = 1, 2, 4               # aqg_select_last_routes
@@ -708,6 +709,19 @@ class Device:
         self._chk(self.lib.aqg_grouped_corr(self.ctx, gb.h, xd.tag, C.c_void_p(xd.ptr), yd.tag, C.c_void_p(yd.ptr), C.c_void_p(out.ptr)), "aqg_grouped_corr")
         self.sync()
         return out.to_host()
+
+    def grouped_ewise(self, gb, op, v, s, kind=VEC_SCALAR, layout=LAYOUT_ROW, ot=None, keep=False, out=None):
+        """out[i] = v[i] OP s[group of i] (kind=VEC_SCALAR) or s[group of i] OP v[i] (kind=SCALAR_VEC) for all groups of a build in
+        one launch: `v` in row layout, or (layout=LAYOUT_FLAT) in the flat layout; `s`: one scalar per group"""
+        vd, sd = self._dev(v), self._dev(s)
+        if ot is None:
+            ot = self.lib.aqg_ewise_out_dtype(op, *((vd.tag, sd.tag) if kind == VEC_SCALAR else (sd.tag, vd.tag)))
+        if ot == ERROR:
+            raise AqgError("aqg_ewise_out_dtype", ERROR)
+        out = out if out is not None else self.empty(vd.n, TAG2NP[ot])
+        self._chk(self.lib.aqg_grouped_ewise(self.ctx, gb.h, layout, op, kind, vd.tag, C.c_void_p(vd.ptr), sd.tag, C.c_void_p(sd.ptr), ot,
+                                             C.c_void_p(out.ptr)), "aqg_grouped_ewise")
+        return out if keep else out.to_host()
 
     # -- join
     def join_pairs(self, build, probe):

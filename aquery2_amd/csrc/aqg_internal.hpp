@@ -157,6 +157,8 @@ struct aqg_groupby;
 size_t aqg_postproc_ws_bytes(uint32_t n, uint32_t G, int esz);
 int aqg_radix_by_group(aqg_ctx* ctx, aqg_groupby* g, uint32_t* row_ids_dev, const void* x, int esz, void* xout, bool ws_managed);
 int aqg_group_offsets(aqg_ctx* ctx, const aqg_groupby* g, uint32_t* offsets_dev, uint32_t* bsum);
+// segscan.hip: *gid = the group index of every position of the flat layout (n elements, owned and cached by the handle)
+int aqg_flat_gid(aqg_ctx* ctx, aqg_groupby* g, const uint32_t** gid);
 // grouped_reduce.hip: out[g] = op(x[rows whose id in gid_col is g]) through the group-by plans (gid_col: n dense ids in first-occurrence order)
 extern "C" int aqg_grouped_reduce_keyed(aqg_ctx* ctx, aqg_groupby* g, const uint32_t* gid_col, int op, int t, const void* x, void* out_dev);
 

@@ -8,6 +8,7 @@
 // 8-element chunk loaders, so every lane still issues 16-byte loads and stores.
 // HBM-bound: algorithmic bytes per row = sizeof(TL) + sizeof(TR) + sizeof(OT).
 #include "ewise_impl.hpp"
+#include "groupby_handle.hpp"
 
 using namespace aqgew;
 extern template int aqgew::dispatch_ot<int32_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, void*, uint32_t, int);
@@ -16,6 +17,12 @@ extern template int aqgew::dispatch_ot<int64_t>(aqg_ctx*, int, int, int, int, co
 extern template int aqgew::dispatch_ot<uint64_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, void*, uint32_t, int);
 extern template int aqgew::dispatch_ot<float>(aqg_ctx*, int, int, int, int, const void*, int, const void*, void*, uint32_t, int);
 extern template int aqgew::dispatch_ot<double>(aqg_ctx*, int, int, int, int, const void*, int, const void*, void*, uint32_t, int);
+extern template int aqgew::dispatch_got<int32_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, const uint32_t*, void*, uint32_t, int);
+extern template int aqgew::dispatch_got<uint32_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, const uint32_t*, void*, uint32_t, int);
+extern template int aqgew::dispatch_got<int64_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, const uint32_t*, void*, uint32_t, int);
+extern template int aqgew::dispatch_got<uint64_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, const uint32_t*, void*, uint32_t, int);
+extern template int aqgew::dispatch_got<float>(aqg_ctx*, int, int, int, int, const void*, int, const void*, const uint32_t*, void*, uint32_t, int);
+extern template int aqgew::dispatch_got<double>(aqg_ctx*, int, int, int, int, const void*, int, const void*, const uint32_t*, void*, uint32_t, int);
 
 namespace {
 
@@ -69,6 +76,34 @@ int aqg_ewise(aqg_ctx* ctx, int op, int kind, int lt, const void* l, int rt, con
     case AQG_UINT64: return dispatch_ot<uint64_t>(ctx, ot, op, kind, lt, l, rt, r, out, n, vec_ok);
     case AQG_FLOAT: return dispatch_ot<float>(ctx, ot, op, kind, lt, l, rt, r, out, n, vec_ok);
     default: return dispatch_ot<double>(ctx, ot, op, kind, lt, l, rt, r, out, n, vec_ok);
+    }
+}
+
+// out[i] = v[i] OP s[gid(i)] (or s[gid(i)] OP v[i]): `x[val] OP agg(x[val])` of the generated group loop for all groups in one launch.
+// The arithmetic is aqg_ewise's (same compute class, same apply<OP>); only the scalar operand's address differs per element.
+int aqg_grouped_ewise(aqg_ctx* ctx, aqg_groupby* g, int layout, int op, int kind, int vt, const void* v, int st, const void* s_dev, int ot, void* out) {
+    if (!ctx || !g || op < 0 || op > AQG_OP_NE || (layout != AQG_LAYOUT_ROW && layout != AQG_LAYOUT_FLAT))
+        return aqg_fail(ctx, AQG_ERR_ARG, "aqg_grouped_ewise: bad argument");
+    if (kind != AQG_VEC_SCALAR && kind != AQG_SCALAR_VEC) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_grouped_ewise: kind is AQG_VEC_SCALAR or AQG_SCALAR_VEC");
+    if (!g->has_reversemap || !g->has_counts) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_grouped_ewise: handle has no reversemap (use aqg_groupby_build)");
+    const uint32_t n = g->n;
+    if ((!v || !s_dev || !out) && n) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_grouped_ewise: null operand");
+    if (!(dt_is_num(vt) || vt == AQG_BOOL) || !(dt_is_num(st) || st == AQG_BOOL)) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_grouped_ewise: operand dtype");
+    int c = usual_conv(vt, st);
+    if ((c == AQG_FLOAT || c == AQG_DOUBLE) && (op == AQG_OP_MOD || op == AQG_OP_AND || op == AQG_OP_OR || op == AQG_OP_XOR))
+        return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_grouped_ewise: bitwise/mod on floating operands");
+    if (g->ngroups == 0 || n == 0) return AQG_OK;
+    const uint32_t* gid = g->reversemap;
+    if (layout == AQG_LAYOUT_FLAT) AQG_TRY(aqg_flat_gid(ctx, g, &gid));
+    auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const int vec_ok = aligned(v) && aligned(out) && aligned(gid);
+    switch (c) {
+    case AQG_INT32: return dispatch_got<int32_t>(ctx, ot, op, kind, vt, v, st, s_dev, gid, out, n, vec_ok);
+    case AQG_UINT32: return dispatch_got<uint32_t>(ctx, ot, op, kind, vt, v, st, s_dev, gid, out, n, vec_ok);
+    case AQG_INT64: return dispatch_got<int64_t>(ctx, ot, op, kind, vt, v, st, s_dev, gid, out, n, vec_ok);
+    case AQG_UINT64: return dispatch_got<uint64_t>(ctx, ot, op, kind, vt, v, st, s_dev, gid, out, n, vec_ok);
+    case AQG_FLOAT: return dispatch_got<float>(ctx, ot, op, kind, vt, v, st, s_dev, gid, out, n, vec_ok);
+    default: return dispatch_got<double>(ctx, ot, op, kind, vt, v, st, s_dev, gid, out, n, vec_ok);
     }
 }
 

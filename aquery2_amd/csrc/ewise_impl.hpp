@@ -161,6 +161,69 @@ __global__ void __launch_bounds__(256) ewise_kernel(int op, int kind, int lt, co
     }
 }
 
+// ---- aqg_grouped_ewise: the scalar operand is s[gid[i]], one value per group (`x[val] - min(x[val])` for all groups at once) -------------
+// Same lane geometry as ewise_body: E elements per lane per vector (one 16-byte store), UNR vectors per lane, exact grid.  The E group ids
+// of a vector come in as one packed access; the scalars are E dependent loads from a G-element column (cache-resident unless G is large
+// and the ids are in random order).  12 bytes per row for 4-byte elements against 8 of the host-scalar kernel.
+template <int OP, class C, class OT>
+__device__ inline void gewise_body(int kind, int vt, const void* v, int st, const void* s, const uint32_t* gid, OT* out, uint32_t n, int vec_ok) {
+    constexpr int E = elems_for<OT>();
+    constexpr int UNR = ew_unr<E>();
+    const uint32_t nvec = vec_ok ? n / E : 0;
+    const uint32_t stride = blockDim.x;
+    for (uint64_t c = blockIdx.x; c * UNR * blockDim.x < nvec; c += gridDim.x) {
+        const uint32_t v0 = (uint32_t)(c * UNR * blockDim.x) + threadIdx.x;
+        C a[UNR][E], b[UNR][E];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const uint32_t vid = v0 + u * stride;
+            if (vid < nvec) {
+                const size_t base = (size_t)vid * E;
+                const pack<uint32_t, E> ids = *reinterpret_cast<const pack<uint32_t, E>*>(gid + base);
+                load_chunk<C, E>(v, vt, base, a[u]);
+#pragma unroll
+                for (int j = 0; j < E; ++j) b[u][j] = load_one<C>(s, st, ids.v[j]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const uint32_t vid = v0 + u * stride;
+            if (vid < nvec) {
+                pack<OT, E> o;
+#pragma unroll
+                for (int j = 0; j < E; ++j)
+                    o.v[j] = kind == AQG_VEC_SCALAR ? apply<OP, C, OT>(a[u][j], b[u][j]) : apply<OP, C, OT>(b[u][j], a[u][j]);
+                *reinterpret_cast<pack<OT, E>*>(out + (size_t)vid * E) = o;
+            }
+        }
+    }
+    for (uint64_t i = (uint64_t)nvec * E + blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const C a = load_one<C>(v, vt, i), b = load_one<C>(s, st, gid[i]);
+        out[i] = kind == AQG_VEC_SCALAR ? apply<OP, C, OT>(a, b) : apply<OP, C, OT>(b, a);
+    }
+}
+
+template <class C, class OT>
+__global__ void __launch_bounds__(256) gewise_kernel(int op, int kind, int vt, const void* __restrict__ v, int st, const void* __restrict__ s,
+                                                     const uint32_t* __restrict__ gid, OT* __restrict__ out, uint32_t n, int vec_ok) {
+    switch (op) { // wave-uniform
+    case AQG_OP_ADD: gewise_body<AQG_OP_ADD, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_SUB: gewise_body<AQG_OP_SUB, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_MUL: gewise_body<AQG_OP_MUL, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_DIV: gewise_body<AQG_OP_DIV, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_MOD: gewise_body<AQG_OP_MOD, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_AND: gewise_body<AQG_OP_AND, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_OR: gewise_body<AQG_OP_OR, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_XOR: gewise_body<AQG_OP_XOR, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_GT: gewise_body<AQG_OP_GT, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_LT: gewise_body<AQG_OP_LT, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_GE: gewise_body<AQG_OP_GE, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_LE: gewise_body<AQG_OP_LE, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    case AQG_OP_EQ: gewise_body<AQG_OP_EQ, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    default: gewise_body<AQG_OP_NE, C>(kind, vt, v, st, s, gid, out, n, vec_ok); break;
+    }
+}
+
 // host: C++ integer promotion + usual arithmetic conversions -> compute class tag
 inline int promote1(int dt) {
     switch (dt) {
@@ -214,6 +277,22 @@ int launch_ewise(aqg_ctx* ctx, int op, int kind, int lt, const void* l, int rt, 
     }
 }
 
+// the grouped form: exact grid, as launch_ewise
+template <class C, class OT>
+int launch_gewise(aqg_ctx* ctx, int op, int kind, int vt, const void* v, int st, const void* s, const uint32_t* gid, void* out, uint32_t n, int vec_ok) {
+    if constexpr (std::is_same_v<OT, aqg_i128> && std::is_floating_point_v<C>) {
+        return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_grouped_ewise: 128-bit result from floating arithmetic");
+    } else {
+        constexpr int E_ = (int)(16 / sizeof(OT));
+        constexpr int UNR_ = ew_unr<E_>();
+        const uint64_t per_wg = (uint64_t)UNR_ * 256, nvec_ = n / E_;
+        const uint64_t want = (nvec_ + per_wg - 1) / per_wg;
+        unsigned grid = (unsigned)(want < 1 ? 1 : want);
+        hipLaunchKernelGGL((gewise_kernel<C, OT>), dim3(grid), dim3(256), 0, ctx->stream, op, kind, vt, v, st, s, gid, static_cast<OT*>(out), n, vec_ok);
+        return aqg_check_launch(ctx, "gewise_kernel");
+    }
+}
+
 template <class C> int dispatch_ot(aqg_ctx* ctx, int ot, int op, int kind, int lt, const void* l, int rt, const void* r, void* out, uint32_t n, int vec_ok) {
     switch (ot) {
     case AQG_INT8: return launch_ewise<C, int8_t>(ctx, op, kind, lt, l, rt, r, out, n, vec_ok);
@@ -230,6 +309,24 @@ template <class C> int dispatch_ot(aqg_ctx* ctx, int ot, int op, int kind, int l
     case AQG_INT128: case AQG_UINT128: return launch_ewise<C, aqg_i128>(ctx, op, kind, lt, l, rt, r, out, n, vec_ok);
     }
     return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_ewise: unsupported result dtype");
+}
+
+template <class C> int dispatch_got(aqg_ctx* ctx, int ot, int op, int kind, int vt, const void* v, int st, const void* s, const uint32_t* gid, void* out, uint32_t n, int vec_ok) {
+    switch (ot) {
+    case AQG_INT8: return launch_gewise<C, int8_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_INT16: return launch_gewise<C, int16_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_INT32: return launch_gewise<C, int32_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_INT64: return launch_gewise<C, int64_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_UINT8: return launch_gewise<C, uint8_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_UINT16: return launch_gewise<C, uint16_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_UINT32: return launch_gewise<C, uint32_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_UINT64: return launch_gewise<C, uint64_t>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_FLOAT: return launch_gewise<C, float>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_DOUBLE: return launch_gewise<C, double>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_BOOL: return launch_gewise<C, bool>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    case AQG_INT128: case AQG_UINT128: return launch_gewise<C, aqg_i128>(ctx, op, kind, vt, v, st, s, gid, out, n, vec_ok);
+    }
+    return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_grouped_ewise: unsupported result dtype");
 }
 
 

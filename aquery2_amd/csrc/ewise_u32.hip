@@ -1,3 +1,4 @@
-// ewise_u32.hip -- the aqg_ewise kernels whose arithmetic runs in uint32_t (see ewise_impl.hpp)
+// ewise_u32.hip -- the aqg_ewise and aqg_grouped_ewise kernels whose arithmetic runs in uint32_t (see ewise_impl.hpp)
 #include "ewise_impl.hpp"
 template int aqgew::dispatch_ot<uint32_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, void*, uint32_t, int);
+template int aqgew::dispatch_got<uint32_t>(aqg_ctx*, int, int, int, int, const void*, int, const void*, const uint32_t*, void*, uint32_t, int);

@@ -395,6 +395,21 @@ int flat_esz(int t) {
 
 } // namespace
 
+// the group index of every flat position, cached in the handle (one segmented pass over the start bitmap on first use; resets the workspace then)
+int aqg_flat_gid(aqg_ctx* ctx, aqg_groupby* g, const uint32_t** gid) {
+    AQG_TRY(ensure_flat(ctx, g));
+    if (!g->flat_gid_valid) {
+        const uint32_t n = g->n;
+        AQG_TRY(aqg_ws_reset(ctx));
+        AQG_TRY(aqg_ws_ensure(ctx, carry_ws_bytes(n) * 2 + 65536));
+        AQG_TRY(aqg_dev_realloc(ctx, &g->flat_gid, &g->cap_flat_gid, ((size_t)n + 4) * 4));
+        AQG_TRY((seg_prefix<uint8_t, none_alg, SW_GID>(ctx, g, nullptr, n, g->flat_gid)));
+        g->flat_gid_valid = true;
+    }
+    *gid = g->flat_gid;
+    return AQG_OK;
+}
+
 extern "C" {
 
 const uint32_t* aqg_groupby_offsets(aqg_groupby* g) {
@@ -487,12 +502,9 @@ int aqg_grouped_reduce_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const v
         });
     }
     // VAR / STDDEV: through the group-by plans, keyed by the group index of every flat position
-    if (!g->flat_gid_valid) {
-        AQG_TRY(aqg_dev_realloc(ctx, &g->flat_gid, &g->cap_flat_gid, ((size_t)n + 4) * 4));
-        AQG_TRY((seg_prefix<uint8_t, none_alg, SW_GID>(ctx, g, nullptr, n, g->flat_gid)));
-        g->flat_gid_valid = true;
-    }
-    return aqg_grouped_reduce_keyed(ctx, g, g->flat_gid, op, t, xflat, out_dev);
+    const uint32_t* gid;
+    AQG_TRY(aqg_flat_gid(ctx, g, &gid));
+    return aqg_grouped_reduce_keyed(ctx, g, gid, op, t, xflat, out_dev);
 }
 
 } // extern "C"

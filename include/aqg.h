@@ -296,6 +296,18 @@ int aqg_grouped_scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const voi
 int aqg_grouped_scan(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* x, uint32_t w, void* out_flat);
 int aqg_grouped_reduce_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xflat, void* out_dev);
 int aqg_grouped_corr(aqg_ctx* ctx, aqg_groupby* g, int tx, const void* x, int ty, const void* y, double* out_dev);
+/* `x[val] OP agg(x[val])` of the generated loop (`price - min(price)`, `price / first(price)` under GROUP BY) for all groups in ONE launch:
+ * out[i] = v[i] OP s[gid(i)]  (kind AQG_VEC_SCALAR)   or   s[gid(i)] OP v[i]  (kind AQG_SCALAR_VEC)
+ * v, out: n = aqg_groupby_nrows(g) elements in ROW layout (gid = the build's reversemap) or in the FLAT layout
+ * (gid = group index of the flat position); s: DEVICE column of G elements of dtype st, one per group.
+ * Every group's slice of `out` equals, bit for bit, aqg_ewise over that group's slice of v with the host scalar s[g]: the same compute
+ * type, operators (aqg_ewise's ops), division rules and result conversion, every result dtype aqg_ewise accepts.  vt / st: numeric or
+ * bool (128-bit operands: AQG_ERR_DTYPE); a handle of aqg_groupby_agg or kind AQG_VEC_VEC: AQG_ERR_ARG; G == 0: AQG_OK, nothing written.
+ * AQG_LAYOUT_FLAT: the first such call through a handle makes the group index of every flat position (n * 4 bytes kept by the handle, one
+ * segmented pass) and, like the grouped scans, resets the context's workspace for it; later calls launch the one kernel only. */
+enum { AQG_LAYOUT_ROW = 0, AQG_LAYOUT_FLAT = 1 };
+int aqg_grouped_ewise(aqg_ctx* ctx, aqg_groupby* g, int layout, int op, int kind,
+                      int vt, const void* v, int st, const void* s_dev, int ot, void* out);
 
 /* fused single-pass group-by + aggregates (h2o Q1..Q5 shape): reads each key and value
  * column exactly once.  Group order = first occurrence, as aqg_groupby_build.  Result j

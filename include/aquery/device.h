@@ -61,8 +61,11 @@ struct GroupCtx {
     uint32_t* row_ids = nullptr;   // [n]   host address (device copy registered)
     std::vector<VCol> vcols;
     std::map<std::array<uint64_t, 6>, int> memo;             // (kind, op, operand columns, window / scalar bits) -> column, made once for all groups
-    struct ScalarUse { uint64_t bits[2]; int vcol; bool varies; };
-    std::map<std::array<uint64_t, 4>, ScalarUse> smemo;      // element-wise (column OP scalar): poisoned once the scalar differs between groups
+    // element-wise (column OP scalar).  The first group's scalar makes a constant-scalar column; once a later group's scalar differs the
+    // use `varies`, and either the scalar's source was found among the cached per-group aggregates (`gvcol`: the column made by
+    // aqg_grouped_ewise from `scol`, the G scalars it was computed with) or every later group takes the per-group path
+    struct ScalarUse { uint64_t bits[2]; int vcol; bool varies; uint32_t g0; int gvcol; std::vector<unsigned char> scol; };
+    std::map<std::array<uint64_t, 4>, ScalarUse> smemo;
     // (column, op) -> G result slots of 16 bytes, filled for ALL groups by one kernel on first request
     std::map<std::pair<int, int>, std::vector<unsigned char>> cache;
     std::map<std::pair<int, int>, std::vector<double>> corr_cache;
@@ -252,17 +255,27 @@ public:
         release(tl); release(tr);
         return vcol_new(c, key, o);
     }
-    // column OP scalar (kind: AQG_VEC_SCALAR / AQG_SCALAR_VEC).  A scalar that differs between the groups (`x[val] - min(x[val])`) cannot be
-    // answered for all groups at once: returns -1 from the second value on and the caller takes the per-group path
-    int vcol_ewise_scalar(GroupCtx* c, int op, int kind, int v, int st, const void* scalar, size_t ssz, int ot) {
+    // column OP scalar (kind: AQG_VEC_SCALAR / AQG_SCALAR_VEC) for group g, whose slice has `vsize` elements.  A scalar that is the same for
+    // every group gives ONE constant-scalar column.  A scalar that differs between the groups (`x[val] - min(x[val])`) is looked up among
+    // the per-group aggregates this grouping already holds: found, the operator runs once for all groups with a per-group scalar column
+    // (vcol_ewise_grouped); not found (a scalar derived on the host), -1 and the caller takes the per-group path
+    size_t grouped_ewise_calls = 0;   // aqg_grouped_ewise calls made so far
+    size_t scalar_fallbacks = 0;      // times vcol_ewise_scalar sent its caller to the per-group path
+    int vcol_ewise_scalar(GroupCtx* c, int op, int kind, int v, int st, const void* scalar, size_t ssz, int ot, uint32_t g, uint32_t vsize) {
         uint64_t bits[2] = {0, 0};
         std::memcpy(bits, scalar, ssz < 16 ? ssz : 16);
         const std::array<uint64_t, 4> key{(uint64_t)op | ((uint64_t)kind << 32), (uint64_t)v, (uint64_t)st, (uint64_t)ot};
         auto it = c->smemo.find(key);
         if (it != c->smemo.end()) {
-            if (it->second.varies) return -1;
-            if (it->second.bits[0] == bits[0] && it->second.bits[1] == bits[1]) return it->second.vcol;
-            it->second.varies = true;
+            GroupCtx::ScalarUse& u = it->second;
+            if (!u.varies) {
+                if (u.bits[0] == bits[0] && u.bits[1] == bits[1]) return u.vcol;
+                u.varies = true;
+                if (ssz <= 8 && vsize == c->counts[g]) u.gvcol = vcol_ewise_grouped(c, op, kind, v, st, ssz, ot, u, g, scalar);
+            }
+            // answered from the expanded column only when this group's scalar IS the element the column was computed with
+            if (u.gvcol >= 0 && vsize == c->counts[g] && std::memcmp(&u.scol[(size_t)g * ssz], scalar, ssz) == 0) return u.gvcol;
+            ++scalar_fallbacks;
             return -1;
         }
         VCol o; o.tag = ot; o.layout = c->vcols[v].layout;
@@ -276,8 +289,38 @@ public:
         release(tv);
         c->vcols.push_back(o);
         const int id = (int)c->vcols.size() - 1;
-        c->smemo[key] = GroupCtx::ScalarUse{{bits[0], bits[1]}, id, false};
+        c->smemo[key] = GroupCtx::ScalarUse{{bits[0], bits[1]}, id, false, g, -1, {}};
         return id;
+    }
+    // The scalar of group u.g0 was u.bits and that of group g is `scalar`: the cached aggregate (column, op) whose slots hold exactly those
+    // two values is taken for the scalar's source, its G slots become the scalar column (u.scol, uploaded once) and aqg_grouped_ewise runs
+    // over the whole column in its layout.  A wrong guess is harmless: the caller compares every group's scalar with u.scol before it
+    // uses the result.  Returns the column, or -1 when no aggregate matches.  Called once per ScalarUse (when it starts to vary).
+    // Only the first ssz bytes of a 16-byte slot are compared, whatever the slot's own type: an int scalar can match the low half of a
+    // 64-bit or double slot.  That is still sound -- u.scol then holds those very bytes, and the per-group comparison decides.
+    int vcol_ewise_grouped(GroupCtx* c, int op, int kind, int v, int st, size_t ssz, int ot, GroupCtx::ScalarUse& u, uint32_t g, const void* scalar) {
+        const std::pair<const std::pair<int, int>, std::vector<unsigned char>>* src = nullptr;
+        for (const auto& kv : c->cache)
+            if (std::memcmp(&kv.second[(size_t)u.g0 * 16], u.bits, ssz) == 0 && std::memcmp(&kv.second[(size_t)g * 16], scalar, ssz) == 0) { src = &kv; break; }
+        if (!src) return -1;
+        u.scol.resize((size_t)c->G * ssz);
+        for (uint32_t k = 0; k < c->G; ++k) std::memcpy(&u.scol[(size_t)k * ssz], &src->second[(size_t)k * 16], ssz);
+        const std::array<uint64_t, 6> key{3, (uint64_t)op | ((uint64_t)kind << 32) | ((uint64_t)st << 40), (uint64_t)v,
+                                          (uint64_t)(uint32_t)src->first.first, (uint64_t)(uint32_t)src->first.second, (uint64_t)ot};
+        VCol o; o.tag = ot; o.layout = c->vcols[v].layout;
+        void *tv = nullptr, *ds = nullptr;
+        const void* dv = o.layout ? c->vcols[v].dptr : vcol_row_ptr(c, v, &tv);
+        int rc = aqg_malloc(ctx(), (size_t)c->n * esz(ot) + 16, &o.dptr);
+        if (rc == AQG_OK) rc = aqg_malloc(ctx_, u.scol.size() + 16, &ds);
+        if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+        rc = aqg_h2d(ctx_, ds, u.scol.data(), u.scol.size());
+        if (rc != AQG_OK) die("aqg_h2d", rc, ctx_);
+        ++grouped_ewise_calls;
+        rc = aqg_grouped_ewise(ctx_, c->handle, o.layout ? AQG_LAYOUT_FLAT : AQG_LAYOUT_ROW, op, kind, c->vcols[v].tag, dv, st, ds, ot, o.dptr);
+        if (rc != AQG_OK) die("aqg_grouped_ewise", rc, ctx_);
+        release(tv);
+        aqg_free(ctx_, ds);
+        return vcol_new(c, key, o);
     }
     void free_vcols(GroupCtx* c) {
         for (auto& v : c->vcols) { if (v.dptr) aqg_free(ctx(), v.dptr); if (v.flat) aqg_free(ctx(), v.flat); }

@@ -307,8 +307,8 @@ inline void device_binary(int op, const L& l, const R& r, vector_type<RT>& ret) 
             GroupCtx* gc = e->dgroup;
             const uint32_t g = e->dg;
             int v;
-            if constexpr (lcol) { using TS = std::remove_cv_t<R>; TS sc = r; v = rt.vcol_ewise_scalar(gc, op, AQG_VEC_SCALAR, e->dv, tag_of<TS>::value, &sc, sizeof(TS), ot); }
-            else { using TS = std::remove_cv_t<L>; TS sc = l; v = rt.vcol_ewise_scalar(gc, op, AQG_SCALAR_VEC, e->dv, tag_of<TS>::value, &sc, sizeof(TS), ot); }
+            if constexpr (lcol) { using TS = std::remove_cv_t<R>; TS sc = r; v = rt.vcol_ewise_scalar(gc, op, AQG_VEC_SCALAR, e->dv, tag_of<TS>::value, &sc, sizeof(TS), ot, g, l.size); }
+            else { using TS = std::remove_cv_t<L>; TS sc = l; v = rt.vcol_ewise_scalar(gc, op, AQG_SCALAR_VEC, e->dv, tag_of<TS>::value, &sc, sizeof(TS), ot, g, r.size); }
             if (v >= 0) {
                 rt.defer_slice(ret.container, (size_t)n * sizeof(RT), gc, g, v);
                 if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
