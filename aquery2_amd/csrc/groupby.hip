@@ -205,6 +205,9 @@ int make_agg_plan(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint3
     p.use_lds = hint <= 3072 && !ks.wide;   // wide tuples compare against HBM-resident rows: HBM mode
     p.lcap = p.use_lds ? next_pow2((uint64_t)(hint < 64 ? 64 : hint) * 4 / 3 + 1) : 0;
     if (p.use_lds && p.lcap < 256) p.lcap = 256;
+    // the star join's LDS also holds the dimension side (up to 64 KiB): its group table stops at 2048 slots, and the groups beyond its
+    // load limit (1536) are summed in the global table -- correct up to the 3072 groups the call promises, slower beyond 1536
+    if (p.plan.sj && p.lcap > 2048) p.lcap = 2048;
     p.lds_slot_bytes = 8 + 8 * (size_t)as.nacc + (p.k32 ? 0 : 4) + (p.plan.need_count ? 4 : 0);
     if (p.use_lds && (size_t)(p.lcap + 1) * p.lds_slot_bytes > LDS_SMALL) { p.use_lds = false; p.lcap = 0; }
     if (p.plan.sj && !(p.use_lds && p.k32))
@@ -496,6 +499,7 @@ int run_agg(aqg_ctx* ctx, const KeySpec& ks_in, const Plan& plan_in, uint32_t n,
 int aqg_run_with_retry(aqg_ctx* ctx, const KeySpec& ks, const Plan& plan, uint32_t n, uint32_t hint, bool for_build, aqg_groupby* h,
                    GTable* gt_out, uint32_t** slot_gid_out, uint32_t** occ_out, DenseOut* dense_out) {
     uint64_t cur = hint ? hint : (h->hint_used ? h->hint_used : 1024);
+    if (plan.sj && !hint && cur > 3072) cur = 3072;                   // (a handle that served a larger group-by before)
     if (!hint && !h->hint_used && n >= (1u << 22) && !plan.sj) { const uint64_t e = aqg_estimate_groups(ctx, ks, n); if (e > cur) cur = e; }
     for (int attempt = 0; attempt < 12; ++attempt) {
         if (cur > n && n) cur = n;
@@ -505,7 +509,8 @@ int aqg_run_with_retry(aqg_ctx* ctx, const KeySpec& ks, const Plan& plan, uint32
         if (rc != AQG_ERR_OVERFLOW) { if (rc == AQG_OK) h->hint_used = (uint32_t)cur; return rc; }
         if (n && cur >= n) return aqg_fail(ctx, AQG_ERR_OVERFLOW, "group-by: table overflow at full capacity");
         // (x16 -- but not past 2^25 in one step: beyond it packed keys leave the partition plans)
-        cur = cur < (1ull << 25) && cur * 16 > (1ull << 25) ? (1ull << 25) : cur * 16;
+        const uint64_t next = cur < (1ull << 25) && cur * 16 > (1ull << 25) ? (1ull << 25) : cur * 16;
+        cur = plan.sj && cur < 3072 && next > 3072 ? 3072 : next;     // (the star join takes no more: its last step is its limit, whatever the hint was)
     }
     return aqg_fail(ctx, AQG_ERR_OVERFLOW, "group-by: table overflow");
 }

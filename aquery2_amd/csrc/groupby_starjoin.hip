@@ -103,16 +103,23 @@ __global__ void __launch_bounds__(256) starjoin_kernel(const uint32_t* __restric
     // |product| < 2^32 * wmax; when this workgroup's rows cannot overflow 63 bits of that, ONE 64-bit LDS atomic per row carries
     // the whole product (split into its halves at the merge); otherwise the halves are summed separately
     const bool one_acc = (uint64_t)wmax * ((uint64_t)(c_hi - c_lo) * R + R) < (1ull << 31);
+    // the 16-byte loads need 16-byte aligned columns; a column view that starts at an odd element takes 4-byte loads
+    const bool aligned = ((reinterpret_cast<uintptr_t>(sj.fk) | reinterpret_cast<uintptr_t>(gkeys) | reinterpret_cast<uintptr_t>(sj.vals)) & 15) == 0;
     for (uint32_t c = c_lo + threadIdx.x; c < c_hi; c += blockDim.x) {
         const size_t base = (size_t)c * R;
         uint32_t f[R], g[R], v[R];
+        if (aligned) {
 #pragma unroll
-        for (int h = 0; h < R / 4; ++h) {
-            const pack<uint32_t, 4> f4 = *reinterpret_cast<const pack<uint32_t, 4>*>(sj.fk + base + 4 * h);
-            const pack<uint32_t, 4> g4 = *reinterpret_cast<const pack<uint32_t, 4>*>(gkeys + base + 4 * h);
-            const pack<uint32_t, 4> v4 = *reinterpret_cast<const pack<uint32_t, 4>*>(sj.vals + base + 4 * h);
+            for (int h = 0; h < R / 4; ++h) {
+                const pack<uint32_t, 4> f4 = *reinterpret_cast<const pack<uint32_t, 4>*>(sj.fk + base + 4 * h);
+                const pack<uint32_t, 4> g4 = *reinterpret_cast<const pack<uint32_t, 4>*>(gkeys + base + 4 * h);
+                const pack<uint32_t, 4> v4 = *reinterpret_cast<const pack<uint32_t, 4>*>(sj.vals + base + 4 * h);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { f[4 * h + j] = f4.v[j]; g[4 * h + j] = g4.v[j]; v[4 * h + j] = v4.v[j]; }
+                for (int j = 0; j < 4; ++j) { f[4 * h + j] = f4.v[j]; g[4 * h + j] = g4.v[j]; v[4 * h + j] = v4.v[j]; }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < R; ++j) { f[j] = sj.fk[base + j]; g[j] = gkeys[base + j]; v[j] = sj.vals[base + j]; }
         }
         uint32_t ds[R], dk[R], gs[R];
         uint64_t gw[R];

@@ -1,8 +1,9 @@
 // join.hip -- hash equi-join on one integer key column.
 // New functionality: the reference emits joins as SQL for MonetDB (engine/ast.py:874-1085) and has no
 // C++ join, so the contract is this library's own: inner join, pairs ordered by probe row,
-// then by build row ascending (what a probe loop over an aq_map<key, rows> yields).  PARITY UNPINNED
-// by the reference; checked against the oracle's restatement.
+// then by build row ascending (what a probe loop over an aq_map<key, rows> yields).  The reference pins none of it: the
+// specification is tests/join_model.py, held to the oracle's restatement by tests/test_join_model.py and to these kernels by
+// tests/test_gpu_join.py (sentinel keys, wrapping collision chains, duplicates, table routes, error returns).
 //
 //   aqg_join_lookup   unique-key dimension lookup (h2o join + group-by, config 4): an open-addressing
 //                     table {key -> lowest build row} in HBM (L2-resident for small dimensions); the

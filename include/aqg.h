@@ -433,7 +433,10 @@ int aqg_scan_sharded(aqg_comm* comm, int op, int t, const void* x, uint32_t n, u
  * GetLongType) and the sum is aggregations.h:62-70.  All five columns are 4-byte integers; the dimension side has at
  * most 4096 rows (it lives in LDS), unique keys (of duplicates the lowest row wins, as in aqg_join_lookup); fact rows
  * without a partner are dropped (inner join).  Result: a group-by handle whose keys / first rows are in first-occurrence
- * order among the JOINED rows and whose aqg_groupby_agg_result(h, 0) is the 128-bit sum per group.  At most 3072 groups. */
+ * order among the JOINED rows and whose aqg_groupby_agg_result(h, 0) is the 128-bit sum per group.  At most 3072 groups,
+ * counted among the joined rows (group keys of rows without a partner do not count), whatever max_groups_hint says: 0 or a hint
+ * that turns out too small is grown up to 3072; more groups than that return AQG_ERR_ARG, and so does a hint above 3072 unless
+ * the call has fewer rows than that (a hint is never taken to be larger than n).                                                  */
 int aqg_join_groupby_sum(aqg_ctx* ctx, int key_dtype, const void* dim_keys, int dim_val_dtype, const void* dim_vals, uint32_t nb,
                          const void* fact_fk, int group_key_dtype, const void* group_keys, int val_dtype, const void* fact_vals,
                          uint32_t n, uint32_t max_groups_hint, aqg_groupby** out);
