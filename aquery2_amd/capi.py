@@ -36,6 +36,13 @@ MEDIAN_PROTOTYPES = {
     "aqg_grouped_median_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "aqg_select_last_routes": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
 }
+# ctypes prototypes of the count-distinct entries (applied by load_library)
+DISTINCT_PROTOTYPES = {
+    "aqg_count_distinct": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)],
+    "aqg_grouped_count_distinct": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_grouped_count_distinct_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_distinct_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+}
 PLAN_FAST_LDS, PLAN_SMALL_LDS, PLAN_BIG_LDS, PLAN_DENSE, PLAN_PART_ONE, PLAN_PART_TWO, PLAN_PART_ROUND1, PLAN_PART_WIDE, PLAN_SORTED_TAIL, PLAN_HBM_TABLE, PLAN_BUILD_PARTITIONED, PLAN_GID_PARTITION, PLAN_PACKED_VALUES, PLAN_RANGE_PARTITIONS, PLAN_ROW_EMIT, PLAN_PACKED_KEYS, PLAN_BUILD_LOOKUP = (1 << i for i in range(17))
 
 
@@ -70,7 +77,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in MEDIAN_PROTOTYPES.items():
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -591,6 +598,29 @@ class Device:
         r, p = C.c_uint32(), C.c_uint32()
         self._chk(self.lib.aqg_select_last_routes(self.ctx, C.byref(r), C.byref(p)), "aqg_select_last_routes")
         return r.value, p.value
+
+    # -- count distinct (include/aqg.h, count distinct section)
+    def count_distinct(self, x):
+        """count(distinct x) of a column: -0.0 == +0.0, every NaN row a value of its own (0 for an empty column)"""
+        xd = self._dev(x)
+        out = C.c_uint32()
+        self._chk(self.lib.aqg_count_distinct(self.ctx, xd.tag, xd.ptr, xd.n, C.byref(out)), "aqg_count_distinct")
+        return out.value
+
+    def grouped_count_distinct(self, gb, x, layout="row", keep=False, out=None):
+        """count(distinct x) of every group of a build (np.uint32): `x` in row layout, or (layout="flat") already in the flat layout"""
+        assert layout in ("row", "flat")
+        xd = self._dev(x)
+        out = out if out is not None else self.empty(gb.ngroups, np.uint32)
+        fn = self.lib.aqg_grouped_count_distinct_flat if layout == "flat" else self.lib.aqg_grouped_count_distinct
+        self._chk(fn(self.ctx, gb.h, xd.tag, xd.ptr, out.ptr), "aqg_grouped_count_distinct")
+        return out if keep else out.to_host()
+
+    def distinct_last(self):
+        """(rows per tile, groups of the last count-distinct call that crossed a tile edge, (group, value) pairs they left)"""
+        t, c, p = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.aqg_distinct_last(self.ctx, C.byref(t), C.byref(c), C.byref(p)), "aqg_distinct_last")
+        return t.value, c.value, p.value
 
     # -- group by
     def _keyargs(self, keys):

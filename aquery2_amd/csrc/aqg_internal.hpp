@@ -51,6 +51,12 @@ struct aqg_ctx {
     bool sort_passes_on_dev = false;
     uint32_t* sort_passes_dev = nullptr;
     uint32_t* select_ctl = nullptr;              // aqg_median / aqg_grouped_median: control words of the last call (routes, passes, the flat call's result)
+    // aqg_count_distinct / aqg_grouped_count_distinct: control words of the last call (pairs, crossing groups, the flat call's offsets and
+    // result), the pair list (grow-only) and the flat call's handle for the group-by over it
+    uint32_t* distinct_ctl = nullptr;
+    void* distinct_pairs = nullptr;
+    size_t distinct_pairs_cap = 0;
+    struct aqg_groupby* distinct_scratch = nullptr;
     // pinned host staging for small results
     void* host_stage = nullptr;
     size_t host_stage_cap = 0;

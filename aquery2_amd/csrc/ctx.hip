@@ -107,6 +107,9 @@ void aqg_ctx_destroy(aqg_ctx* ctx) {
     if (ctx->rank_bm) hipFree(ctx->rank_bm);
     if (ctx->sort_passes_dev) hipFree(ctx->sort_passes_dev);
     if (ctx->select_ctl) hipFree(ctx->select_ctl);
+    if (ctx->distinct_scratch) aqg_groupby_destroy(ctx->distinct_scratch);      // (its buffers go to the pool, freed below)
+    if (ctx->distinct_ctl) hipFree(ctx->distinct_ctl);
+    if (ctx->distinct_pairs) hipFree(ctx->distinct_pairs);
     for (auto& e : ctx->pool) hipFree(e.first);
     if (ctx->pool_big) hipFree(ctx->pool_big);
     if (ctx->host_stage) hipHostFree(ctx->host_stage);

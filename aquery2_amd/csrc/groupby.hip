@@ -529,6 +529,7 @@ void aqg_groupby_destroy(aqg_groupby* g) {
     aqg_pool_give(ctx, g->reversemap, g->cap_rows * 4);
     if (g->scratch) aqg_groupby_destroy(g->scratch);
     if (g->scratch2) aqg_groupby_destroy(g->scratch2);
+    if (g->scratch3) aqg_groupby_destroy(g->scratch3);
     aqg_pool_give(ctx, g->flat_off, g->cap_flat_off);
     aqg_pool_give(ctx, g->flat_heads, g->cap_flat_heads);
     aqg_pool_give(ctx, g->flat_short, g->cap_flat_short);

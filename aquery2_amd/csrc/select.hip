@@ -16,12 +16,11 @@
 //          workgroup ever waits for another.
 // A classify kernel over the offsets routes the groups (two compact lists, a per-tile first group); nothing comes back to the host, and
 // the number of launches depends on the dtype's width only.
-#include "aqg_internal.hpp"
-#include "dev_common.hpp"
 #include "groupby_handle.hpp"
-#include "key_image.hpp"
+#include "select_dev.hpp"
 
 namespace {
+using namespace seldev;
 
 constexpr int SB = 256;                       // lanes per workgroup
 constexpr int NWV = SB / 64;
@@ -90,18 +89,6 @@ template <class U> __device__ inline bool both_digits_known(const SelState& st, 
 
 struct OpAnd { template <class T> __device__ T operator()(T a, T b) const { return (T)(a & b); } };
 struct OpOr { template <class T> __device__ T operator()(T a, T b) const { return (T)(a | b); } };
-
-// inclusive sum over the SB lanes of a workgroup (wsum: NWV words of LDS)
-__device__ inline uint32_t block_scan_incl(uint32_t v, uint32_t* wsum) {
-    const int lane = lane_id(), wid = wave_id();
-    const uint32_t incl = wave_scan_incl(v, OpAdd{}, lane);
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wid; ++w) base += wsum[w];
-    __syncthreads();
-    return base + incl;
-}
 
 // One histogram pass of a workgroup over rows [lo, hi) (lo < hi) of x: rows whose image matches `prefix` on `kmask` add their digit at
 // `shift` to h (LDS; NHIST * 256 bins) and fold into vand / vor.  16-byte loads over the aligned middle of the slice, UNR of them in flight per lane; the
@@ -436,8 +423,6 @@ __global__ void __launch_bounds__(SB) select_split_find_kernel(const U* __restri
     }
 }
 
-__global__ void select_flat_offsets_kernel(uint32_t* off, uint32_t n) { off[0] = 0; off[1] = n; }
-
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
 struct SelSwitches { uint32_t small_max, split_min; };
 
@@ -512,15 +497,6 @@ int dispatch_select(aqg_ctx* ctx, int which, int t, const void* x, uint32_t n, c
     }
     return AQG_ERR_DTYPE;
 }
-int select_esz(int t) {
-    switch (t) {
-    case AQG_INT8: case AQG_UINT8: case AQG_BOOL: return 1;
-    case AQG_INT16: case AQG_UINT16: return 2;
-    case AQG_INT32: case AQG_UINT32: case AQG_FLOAT: return 4;
-    case AQG_INT64: case AQG_UINT64: case AQG_DOUBLE: return 8;
-    }
-    return 0;
-}
 SelSwitches select_switches() {
     const aqg_switch_set& s = aqg_switches();
     return SelSwitches{s.select_small_max < SMALL_CAP ? s.select_small_max : SMALL_CAP, s.select_split_min};
@@ -529,7 +505,7 @@ int check_grouped(aqg_ctx* ctx, const aqg_groupby* g, int which, int t, const vo
     if (!ctx || !g) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: bad argument");
     if (!g->has_reversemap || !g->has_counts) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: the handle was not made by aqg_groupby_build");
     if (which != AQG_SEL_LOWER && which != AQG_SEL_UPPER) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: which must be AQG_SEL_LOWER or AQG_SEL_UPPER");
-    if (!select_esz(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "grouped median: 1-, 2-, 4- and 8-byte numeric columns and BOOL");
+    if (!esz_of(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "grouped median: 1-, 2-, 4- and 8-byte numeric columns and BOOL");
     if ((!x || !out) && g->n) return aqg_fail(ctx, AQG_ERR_ARG, "grouped median: null column");
     return AQG_OK;
 }
@@ -541,7 +517,7 @@ extern "C" {
 int aqg_median(aqg_ctx* ctx, int which, int t, const void* x, uint32_t n, void* out_host16) {
     if (!ctx || !out_host16) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_median: bad argument");
     if (which != AQG_SEL_LOWER && which != AQG_SEL_UPPER) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_median: which must be AQG_SEL_LOWER or AQG_SEL_UPPER");
-    if (!select_esz(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_median: 1-, 2-, 4- and 8-byte numeric columns and BOOL");
+    if (!esz_of(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_median: 1-, 2-, 4- and 8-byte numeric columns and BOOL");
     if (!x && n) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_median: null column");
     AQG_CHECK_ROWS(ctx, n, "aqg_median");
     AQG_TRY(ensure_ctl(ctx));
@@ -551,7 +527,7 @@ int aqg_median(aqg_ctx* ctx, int which, int t, const void* x, uint32_t n, void* 
     AQG_TRY(aqg_ws_reset(ctx));
     AQG_TRY(aqg_ws_ensure(ctx, select_ws_bytes(n, 1, sw)));
     uint32_t* ctl = ctx->select_ctl;
-    hipLaunchKernelGGL(select_flat_offsets_kernel, dim3(1), dim3(1), 0, ctx->stream, ctl + CTL_OFF, n);
+    hipLaunchKernelGGL(flat_offsets_kernel, dim3(1), dim3(1), 0, ctx->stream, ctl + CTL_OFF, n);
     AQG_TRY(dispatch_select(ctx, which, t, x, n, ctl + CTL_OFF, 1, sw, ctl + CTL_RESULT));
     return aqg_d2h(ctx, out_host16, ctl + CTL_RESULT, 16);
 }
@@ -577,7 +553,7 @@ int aqg_grouped_median(aqg_ctx* ctx, aqg_groupby* g, int which, int t, const voi
     const uint32_t* off = aqg_groupby_offsets(g);
     if (!off) return AQG_ERR_HIP;
     const SelSwitches sw = select_switches();
-    const int esz = select_esz(t);
+    const int esz = esz_of(t);
     AQG_TRY(aqg_ws_reset(ctx));
     AQG_TRY(aqg_ws_ensure(ctx, (size_t)n * esz + 4096 + aqg_postproc_ws_bytes(n, G, esz) + select_ws_bytes(n, G, sw)));
     unsigned char* xs;

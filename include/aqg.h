@@ -232,6 +232,35 @@ int aqg_grouped_median(aqg_ctx* ctx, struct aqg_groupby* g, int which, int t, co
 int aqg_grouped_median_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, int t, const void* xflat, void* out_dev);
 int aqg_select_last_routes(aqg_ctx* ctx, uint32_t* routes_host, uint32_t* passes_host);
 
+/* ---- count distinct ----------------------------------------------------------
+ * `count(distinct x)`: the generator emits `(x).distinct_size()` (common/types.py:271-277), under GROUP BY `(x[val]).distinct_size()`
+ * inside the generated loop (engine/ast.py:749-784).  Replaces vector_type::distinct_size (server/vector_type.hpp:153-174) and
+ * ColRef::distinct_size (server/table.h:328-332): a std::unordered_set<T> built per call there, per GROUP in the loop.
+ * Result: the size of that set, a uint32_t -- equality by C++ ==, the rule of floating group-by keys above (probed against the
+ * reference headers, tests/golden/ref_distinct.json): integers and BOOL by value; FLOAT / DOUBLE: -0.0 and +0.0 are one value and
+ * every NaN ROW is a value of its own whatever its sign or payload, so the count is (distinct non-NaN values) + (NaN rows).
+ * An empty slice counts 0.
+ * Dtypes: INT8/16/32/64, UINT8/16/32/64, BOOL, FLOAT, DOUBLE; anything else (128-bit integers, dates, strings) returns
+ * AQG_ERR_DTYPE with nothing written.
+ *   aqg_count_distinct               the whole column -> *out_host.  n == 0: AQG_OK and 0.
+ *   aqg_grouped_count_distinct       out_dev[g] for all G groups in group order, x in ROW layout (brought into the flat layout in
+ *                                    workspace first, like aqg_grouped_median)
+ *   aqg_grouped_count_distinct_flat  the same over a column already in the FLAT LAYOUT of the build
+ * The grouped forms need a handle of aqg_groupby_build (as aqg_grouped_scan); a handle of aqg_groupby_agg: AQG_ERR_ARG; G == 0
+ * returns AQG_OK.  The input is never modified.  One algorithm: a pass over tiles of the flat layout counts
+ * every group that lies inside one tile; the groups that cross a tile edge leave (group, value) pairs, which a count-only
+ * aqg_groupby_agg over the pair list folds.  The launches do not depend on the group count.  Asynchronous on the context's stream
+ * except for ONE host round trip per call, the number of pairs (aqg_count_distinct's result rides along; it takes a second one
+ * only when pairs were left).  The pair list
+ * (worst case one pair per row: 4 + sizeof(T) bytes each) is kept by the context and only grows: no allocation in steady state;
+ * when it cannot be had the call returns AQG_ERR_NOMEM with nothing written.
+ * aqg_distinct_last (diagnostic, like aqg_select_last_routes), for the last call on this context: the tile size in rows (a constant,
+ * valid before any call), how many groups crossed a tile edge, and the number of pairs they left.                              */
+int aqg_count_distinct(aqg_ctx* ctx, int t, const void* x, uint32_t n, uint32_t* out_host);
+int aqg_grouped_count_distinct(aqg_ctx* ctx, struct aqg_groupby* g, int t, const void* x, uint32_t* out_dev);
+int aqg_grouped_count_distinct_flat(aqg_ctx* ctx, struct aqg_groupby* g, int t, const void* xflat, uint32_t* out_dev);
+int aqg_distinct_last(aqg_ctx* ctx, uint32_t* tile_rows, uint32_t* crossing_groups, uint64_t* pairs);
+
 /* ---- hash group-by -----------------------------------------------------------
  * Replaces AQHashTable (server/hasher.h:146-199) + set::hashtable_push
  * (server/unordered_dense.h:1117-1147) + HashTableFactory::get (:327-357).

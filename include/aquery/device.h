@@ -369,8 +369,14 @@ public:
     }
     // op(<per-group temporary>) at p: answered from the per-grouping cache (one kernel for all groups).  op: an aqg_redop, or
     // DEFERRED_MEDIAN (`median(col[vecs[g]])`: aqg_grouped_median / aqg_grouped_median_flat, result in the column's own type)
-    static constexpr int DEFERRED_MEDIAN = 1000;
-    size_t grouped_calls = 0;      // aqg_grouped_reduce / _reduce_flat / _median / _median_flat calls made so far (the tests count them)
+    // DEFERRED_DISTINCT (`(col[vecs[g]]).distinct_size()`: aqg_grouped_count_distinct / _flat, a uint32 per group)
+    static constexpr int DEFERRED_MEDIAN = 1000, DEFERRED_DISTINCT = 1001;
+    size_t grouped_calls = 0;      // aqg_grouped_reduce / _reduce_flat / _median / _median_flat / _count_distinct / _count_distinct_flat calls made so far (the tests count them)
+    // the vector of `size` elements at p is a per-group temporary AND all of its group (a shorter view -- subvec shares the address -- is not)
+    bool deferred_whole(const void* p, uint32_t size) {
+        Entry* e = deferred_at(p);
+        return e && e->dgroup->counts[e->dg] == size;
+    }
     bool deferred_reduce(const void* p, int op, void* out16) {
         Entry* ep = deferred_at(p);
         if (!ep) return false;
@@ -380,8 +386,8 @@ public:
         auto hit = c->cache.find(key);
         if (hit == c->cache.end()) {
             const int tag = c->vcols[e.dv].tag;
-            const bool med = op == DEFERRED_MEDIAN;
-            const int ot = med ? tag : aqg_reduce_out_dtype(op, tag);
+            const bool med = op == DEFERRED_MEDIAN, dis = op == DEFERRED_DISTINCT;
+            const int ot = med ? tag : dis ? (int)AQG_UINT32 : aqg_reduce_out_dtype(op, tag);
             const size_t osz = aqg_dtype_size(ot);
             void* dout = nullptr;
             int rc = aqg_malloc(ctx(), (size_t)c->G * 16 + 16, &dout);
@@ -389,13 +395,15 @@ public:
             ++grouped_calls;
             if (c->vcols[e.dv].layout == 1) {
                 rc = med ? aqg_grouped_median_flat(ctx_, c->handle, AQG_SEL_LOWER, tag, c->vcols[e.dv].dptr, dout)
+                   : dis ? aqg_grouped_count_distinct_flat(ctx_, c->handle, tag, c->vcols[e.dv].dptr, static_cast<uint32_t*>(dout))
                          : aqg_grouped_reduce_flat(ctx_, c->handle, op, tag, c->vcols[e.dv].dptr, dout);
-                if (rc != AQG_OK) die(med ? "aqg_grouped_median_flat" : "aqg_grouped_reduce_flat", rc, ctx_);
+                if (rc != AQG_OK) die(med ? "aqg_grouped_median_flat" : dis ? "aqg_grouped_count_distinct_flat" : "aqg_grouped_reduce_flat", rc, ctx_);
             } else {
                 void* tmp = nullptr;
                 const void* dsrc = vcol_row_ptr(c, e.dv, &tmp);
-                rc = med ? aqg_grouped_median(ctx_, c->handle, AQG_SEL_LOWER, tag, dsrc, dout) : aqg_grouped_reduce(ctx_, c->handle, op, tag, dsrc, dout);
-                if (rc != AQG_OK) die(med ? "aqg_grouped_median" : "aqg_grouped_reduce", rc, ctx_);
+                rc = med ? aqg_grouped_median(ctx_, c->handle, AQG_SEL_LOWER, tag, dsrc, dout)
+                   : dis ? aqg_grouped_count_distinct(ctx_, c->handle, tag, dsrc, static_cast<uint32_t*>(dout)) : aqg_grouped_reduce(ctx_, c->handle, op, tag, dsrc, dout);
+                if (rc != AQG_OK) die(med ? "aqg_grouped_median" : dis ? "aqg_grouped_count_distinct" : "aqg_grouped_reduce", rc, ctx_);
                 release(tmp);
             }
             std::vector<unsigned char> packed((size_t)c->G * osz), slots((size_t)c->G * 16, 0);
@@ -577,6 +585,28 @@ struct In {
     In(const In&) = delete;
     In& operator=(const In&) = delete;
 };
+
+// distinct_size() of the `size` elements at `host` (vector_type / ColRef): *out = the size of the reference's std::unordered_set over
+// them (include/aqg.h, count distinct section).  A per-group temporary `col[vecs[g]]` is answered for ALL groups by one grouped call
+// (deferred_reduce); any other vector of a 1-, 2-, 4- or 8-byte numeric type or bool by aqg_count_distinct.  false: the caller keeps
+// its host set -- other element types, and a view SHORTER than its group (it shares the temporary's address)
+template <class T> inline bool count_distinct(const T* host, uint32_t size, bool borrowed, uint32_t* out) {
+    using E = std::remove_cv_t<T>;
+    if constexpr (!on_device<E> || sizeof(E) > 8) return false;
+    else {
+        if (!size) { *out = 0; return true; }
+        Runtime& rt = Runtime::get();
+        if (rt.deferred_at(host)) {
+            alignas(16) unsigned char buf[16];
+            if (!rt.deferred_whole(host, size) || !rt.deferred_reduce(host, Runtime::DEFERRED_DISTINCT, buf)) return false;
+            std::memcpy(out, buf, 4);
+            return true;
+        }
+        In in(host, (size_t)size * sizeof(E), borrowed);
+        check(aqg_count_distinct(rt.ctx(), tag_of<E>::value, in.d, size, out), "aqg_count_distinct");
+        return true;
+    }
+}
 
 } // namespace dev
 } // namespace aq

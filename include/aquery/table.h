@@ -199,7 +199,11 @@ public:
         return sub;
     }
     std::unordered_set<_Ty> distinct_common() const { std::unordered_set<_Ty> s; for (uint32_t i = 0; i < size; ++i) s.insert((*this)[i]); return s; }
-    uint32_t distinct_size() const { return (uint32_t)distinct_common().size(); }
+    uint32_t distinct_size() const {
+        uint32_t r = 0;
+        if (aq::dev::count_distinct(this->container, this->size, this->capacity == 0, &r)) return r;
+        return (uint32_t)distinct_common().size();
+    }
     void out(uint32_t n = 1000, const char* sep = " ") const {
         n = n > size ? size : n;
         std::cout << '(';

@@ -177,7 +177,12 @@ public:
     vector_type<_Ty> getRef() { return vector_type<_Ty>(container, size); }
 
     inline std::unordered_set<value_t> distinct_common() { return std::unordered_set<value_t>(begin(), end()); }
-    uint32_t distinct_size() { return (uint32_t)distinct_common().size(); }
+    // count(distinct): on the device for the numeric types (one grouped call for all groups inside a group loop); the host set otherwise
+    uint32_t distinct_size() {
+        uint32_t r = 0;
+        if (aq::dev::count_distinct(container, size, capacity == 0, &r)) return r;
+        return (uint32_t)distinct_common().size();
+    }
     vector_type<_Ty> distinct_copy() {
         auto d = distinct_common();
         vector_type<_Ty> r((uint32_t)d.size());
