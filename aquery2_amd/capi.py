@@ -43,6 +43,18 @@ DISTINCT_PROTOTYPES = {
     "aqg_grouped_count_distinct_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "aqg_distinct_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
 }
+# ctypes prototypes of the joins on composite and typed keys (applied by load_library)
+JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
+JOIN_ROUTE_PACKED, JOIN_ROUTE_WIDE, JOIN_ROUTE_LDS, JOIN_ROUTE_HBM = 1, 2, 4, 8          # aqg_join_last
+JOIN_KEYS_PROTOTYPES = {
+    "aqg_join_keys_count": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)],
+    "aqg_join_keys_pairs": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                            C.c_uint64, C.POINTER(C.c_uint64)],
+    "aqg_join_keys_lookup": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_join_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "aqg_join_tuple_slots": [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "aqg_gather_fill": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+}
 PLAN_FAST_LDS, PLAN_SMALL_LDS, PLAN_BIG_LDS, PLAN_DENSE, PLAN_PART_ONE, PLAN_PART_TWO, PLAN_PART_ROUND1, PLAN_PART_WIDE, PLAN_SORTED_TAIL, PLAN_HBM_TABLE, PLAN_BUILD_PARTITIONED, PLAN_GID_PARTITION, PLAN_PACKED_VALUES, PLAN_RANGE_PARTITIONS, PLAN_ROW_EMIT, PLAN_PACKED_KEYS, PLAN_BUILD_LOOKUP = (1 << i for i in range(17))
 
 
@@ -77,7 +89,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -85,6 +97,23 @@ def load_library():
 
 def tag_of(a):
     return NP2TAG[np.asarray(a).dtype]
+
+
+def join_tuple_slots(cols, table_slots):
+    """aqg_join_tuple_slots (host code, no GPU): the first slot the join kernels try for every tuple of the HOST key columns `cols`
+    -- numpy arrays, or (tag, array) pairs for DATE / TIME / TIMESTAMP columns given as (n, bytes) uint8 arrays -- in a table of
+    `table_slots` slots"""
+    lib = load_library()
+    pairs = [c if isinstance(c, tuple) else (tag_of(c), c) for c in cols]
+    arrs = [np.ascontiguousarray(a.astype(np.uint8) if np.asarray(a).dtype == np.bool_ else a) for _, a in pairs]
+    n = len(arrs[0]) if arrs else 0
+    dts = (C.c_int * max(1, len(pairs)))(*[t for t, _ in pairs])
+    ptrs = (C.c_void_p * max(1, len(pairs)))(*[a.ctypes.data for a in arrs])
+    out = np.empty(n, np.uint32)
+    rc = lib.aqg_join_tuple_slots(len(pairs), dts, ptrs, n, int(table_slots), out.ctypes.data)
+    if rc != 0:
+        raise AqgError("aqg_join_tuple_slots", rc)
+    return out
 
 
 class DevBuf:
@@ -778,6 +807,52 @@ class Device:
         out = self.empty(pd.n, np.uint32)
         self._chk(self.lib.aqg_join_lookup(self.ctx, bd.tag, C.c_void_p(bd.ptr), C.c_uint32(bd.n), C.c_void_p(pd.ptr),
                                            C.c_uint32(pd.n), C.c_void_p(out.ptr)), "aqg_join_lookup")
+        return out.to_host()
+
+    # -- joins on composite and typed keys (include/aqg.h): a side is a list of key columns (numpy arrays, DevBufs, key_col results)
+    def join_keys_count(self, build_cols, probe_cols, kind=JOIN_INNER):
+        """the number of output rows of the join, in 64 bits (aqg_join_keys_count)"""
+        bd, dts, bp = self._keyargs(build_cols)
+        pd, _, pp = self._keyargs(probe_cols)
+        m = C.c_uint64()
+        self._chk(self.lib.aqg_join_keys_count(self.ctx, kind, len(bd), dts, bp, bd[0].n, pp, pd[0].n, C.byref(m)), "aqg_join_keys_count")
+        return m.value
+
+    def join_keys_pairs(self, build_cols, probe_cols, kind=JOIN_INNER):
+        """(probe_rows, build_rows) of the join as np.uint32 arrays; build_rows is None for JOIN_SEMI / JOIN_ANTI"""
+        bd, dts, bp = self._keyargs(build_cols)
+        pd, _, pp = self._keyargs(probe_cols)
+        m = C.c_uint64()
+        self._chk(self.lib.aqg_join_keys_count(self.ctx, kind, len(bd), dts, bp, bd[0].n, pp, pd[0].n, C.byref(m)), "aqg_join_keys_count")
+        pr = self.empty(m.value, np.uint32)
+        br = self.empty(m.value, np.uint32) if kind in (JOIN_INNER, JOIN_LEFT) else None
+        self._chk(self.lib.aqg_join_keys_pairs(self.ctx, kind, len(bd), dts, bp, bd[0].n, pp, pd[0].n, pr.ptr, br.ptr if br is not None else None,
+                                               m.value, C.byref(m)), "aqg_join_keys_pairs")
+        return pr.to_host()[:m.value], (br.to_host()[:m.value] if br is not None else None)
+
+    def join_keys_lookup(self, build_cols, probe_cols):
+        """np.uint32[np]: the lowest build row whose key tuple equals probe row i, else 0xFFFFFFFF"""
+        bd, dts, bp = self._keyargs(build_cols)
+        pd, _, pp = self._keyargs(probe_cols)
+        out = self.empty(pd[0].n, np.uint32)
+        self._chk(self.lib.aqg_join_keys_lookup(self.ctx, len(bd), dts, bp, bd[0].n, pp, pd[0].n, out.ptr), "aqg_join_keys_lookup")
+        return out.to_host()
+
+    def join_last(self):
+        """(JOIN_ROUTE_* mask, distinct build tuples, table slots) of the last join_keys_* call on this device"""
+        r, g, s = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_join_last(self.ctx, C.byref(r), C.byref(g), C.byref(s)), "aqg_join_last")
+        return r.value, g.value, s.value
+
+    def join_tuple_slots(self, cols, table_slots):
+        return join_tuple_slots(cols, table_slots)
+
+    def gather_fill(self, x, idx, fill=None):
+        """out[i] = fill where idx[i] == 0xFFFFFFFF, else x[idx[i]]; fill None = zero bytes (aqg_gather_fill)"""
+        xd, idd = self._dev(x), self._dev(np.ascontiguousarray(idx, dtype=np.uint32) if not isinstance(idx, DevBuf) else idx)
+        out = self.empty(idd.n, xd.dtype)
+        f = None if fill is None else np.array([fill], dtype=xd.dtype)
+        self._chk(self.lib.aqg_gather_fill(self.ctx, xd.tag, xd.ptr, idd.ptr, idd.n, f.ctypes.data if f is not None else None, out.ptr), "aqg_gather_fill")
         return out.to_host()
 
     # -- timing

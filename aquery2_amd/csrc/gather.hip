@@ -31,6 +31,26 @@ template <class W> __global__ void __launch_bounds__(256) gather_kernel(const W*
     }
 }
 
+// gather_kernel with a select: an index of 0xFFFFFFFF (a probe row without a partner) yields `fill` and reads nothing
+template <class W> __global__ void __launch_bounds__(256) gather_fill_kernel(const W* __restrict__ x, const uint32_t* __restrict__ idx, uint32_t m, W fill, W* __restrict__ out) {
+    const uint32_t nchunk = m >> 2;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    if (aligned) {
+        uint32_t c_lo, c_hi;
+        wg_span(nchunk, c_lo, c_hi);
+        for (uint32_t c = c_lo + threadIdx.x; c < c_hi; c += blockDim.x) {
+            const pack<uint32_t, 4> i4 = *reinterpret_cast<const pack<uint32_t, 4>*>(idx + (size_t)c * 4);
+            pack<W, 4> o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o.v[j] = i4.v[j] == 0xFFFFFFFFu ? fill : x[i4.v[j]];
+            *reinterpret_cast<pack<W, 4>*>(out + (size_t)c * 4) = o;
+        }
+        for (uint32_t i = (nchunk << 2) + blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) { const uint32_t j = idx[i]; out[i] = j == 0xFFFFFFFFu ? fill : x[j]; }
+    } else {
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) { const uint32_t j = idx[i]; out[i] = j == 0xFFFFFFFFu ? fill : x[j]; }
+    }
+}
+
 __global__ void __launch_bounds__(CB) mask_count_kernel(const uint8_t* __restrict__ mask, uint32_t n, uint32_t* __restrict__ tile_cnt) {
     __shared__ uint32_t ws[4];
     uint32_t base = blockIdx.x * CTS + threadIdx.x * CIT, c = 0;
@@ -180,6 +200,25 @@ int aqg_gather(aqg_ctx* ctx, int t, const void* x, const uint32_t* idx, uint32_t
     default: return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_gather: dtype");
     }
     return aqg_check_launch(ctx, "gather_kernel");
+}
+
+int aqg_gather_fill(aqg_ctx* ctx, int t, const void* x, const uint32_t* idx, uint32_t m, const void* fill_host, void* out) {
+    if (!ctx || ((!x || !idx || !out) && m)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_gather_fill: bad argument");
+    const size_t esz = aqg_dtype_size(t);
+    if (esz != 1 && esz != 2 && esz != 4 && esz != 8 && esz != 16) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_gather_fill: dtype");
+    if (m == 0) return AQG_OK;
+    AQG_CHECK_ROWS(ctx, m, "aqg_gather_fill");
+    w128 f = {0, 0};
+    if (fill_host) memcpy(&f, fill_host, esz);
+    unsigned grid = aqg_grid(ctx, m, 256, 4, 16);
+    switch (esz) {
+    case 1: hipLaunchKernelGGL((gather_fill_kernel<uint8_t>), dim3(grid), dim3(256), 0, ctx->stream, (const uint8_t*)x, idx, m, (uint8_t)f.a, (uint8_t*)out); break;
+    case 2: hipLaunchKernelGGL((gather_fill_kernel<uint16_t>), dim3(grid), dim3(256), 0, ctx->stream, (const uint16_t*)x, idx, m, (uint16_t)f.a, (uint16_t*)out); break;
+    case 4: hipLaunchKernelGGL((gather_fill_kernel<uint32_t>), dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t*)x, idx, m, (uint32_t)f.a, (uint32_t*)out); break;
+    case 8: hipLaunchKernelGGL((gather_fill_kernel<uint64_t>), dim3(grid), dim3(256), 0, ctx->stream, (const uint64_t*)x, idx, m, f.a, (uint64_t*)out); break;
+    default: hipLaunchKernelGGL((gather_fill_kernel<w128>), dim3(grid), dim3(256), 0, ctx->stream, (const w128*)x, idx, m, f, (w128*)out); break;
+    }
+    return aqg_check_launch(ctx, "gather_fill_kernel");
 }
 
 int aqg_compact(aqg_ctx* ctx, int t, const void* x, const uint8_t* mask, uint32_t n, void* out, uint32_t* m_host) {

@@ -183,6 +183,9 @@ int aqg_scan_resume(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, cons
  * ColRef::operator[](const std::vector<bool>&) server/table.h:190-198 (as a true
  * stream compaction; the reference's N-junk prefix, defect D11, is not kept)   */
 int aqg_gather(aqg_ctx* ctx, int t, const void* x, const uint32_t* idx, uint32_t m, void* out);
+/* the gather that knows about missing rows (the build columns of a LEFT join, of a look-up with misses):
+ * out[i] = idx[i] == 0xFFFFFFFF ? *fill_host : x[idx[i]]   (elements of 1, 2, 4, 8, 16 bytes; fill_host NULL = zero bytes) */
+int aqg_gather_fill(aqg_ctx* ctx, int t, const void* x, const uint32_t* idx, uint32_t m, const void* fill_host, void* out);
 int aqg_compact(aqg_ctx* ctx, int t, const void* x, const uint8_t* mask, uint32_t n,
                 void* out, uint32_t* m_host);
 /* row ids of set mask entries, ascending (selection vector for multi-column filters) */
@@ -384,6 +387,48 @@ int aqg_join_pairs(aqg_ctx* ctx, int t, const void* build_keys, uint32_t nb,
  * equals probe_keys[i], or 0xFFFFFFFF                                            */
 int aqg_join_lookup(aqg_ctx* ctx, int t, const void* build_keys, uint32_t nb,
                     const void* probe_keys, uint32_t np, uint32_t* build_row_of_probe);
+
+/* ---- joins on composite and typed keys: inner, left outer, semi, anti (the contract: tests/join_keys_model.py)
+ * A key is a tuple of 1..8 columns; ONE dtype list serves both sides (column k of the build side and of the probe side have
+ * key_dtypes[k]).  Accepted: INT8/16/32/64, UINT8/16/32/64, BOOL, FLOAT, DOUBLE, DATE, TIME, TIMESTAMP, INT128, UINT128 -- anything
+ * else (AQG_STR included) returns AQG_ERR_DTYPE with nothing written; string keys join through codes: ONE aqg_str_encode call over
+ * both tables' strings (build rows first, then probe rows), the two halves of the code column passed as UINT32.  A tuple that
+ * normalises to more than eight integer columns (TIMESTAMP and 128-bit count two) returns AQG_ERR_ARG, as the group-by does.
+ * Equality is the group-by's, column by column: integers and BOOL by value, DATE its 4 bytes, TIME its 7 field bytes (the padding
+ * byte may differ between the sides), TIMESTAMP date plus time, 128-bit all 16 bytes, FLOAT / DOUBLE by C++ `==`: -0.0 equals
+ * +0.0 and a NaN equals NOTHING -- a probe row with a NaN in any floating key matches no build row (it is unmatched under LEFT and
+ * ANTI), a build row with one is in no pair.  No key value is reserved (the all-ones tuples are ordinary keys).
+ * With c_i = the number of build rows equal to probe row i:
+ *   INNER  every matching pair, by probe row, then by ascending build row (one integer key: identical to aqg_join_pairs); m = sum c_i
+ *   LEFT   as INNER, plus one pair (i, 0xFFFFFFFF) in probe-row order for every probe row with c_i == 0;          m = sum max(c_i, 1)
+ *   SEMI   the probe rows with c_i > 0, ascending, each once; build_rows_out is neither read nor written and may be NULL
+ *   ANTI   the probe rows with c_i == 0, ascending; build_rows_out as for SEMI
+ * nb == 0: INNER and SEMI give 0, LEFT np pairs (i, 0xFFFFFFFF), ANTI all np rows; np == 0: 0 for every kind.
+ * *m_host is exact in 64 bits.  aqg_join_keys_pairs with probe_rows_out == NULL only counts; beyond AQG_MAX_ROWS output rows, or
+ * beyond `capacity`, it returns AQG_ERR_OVERFLOW with *m_host = the count and nothing written.
+ * aqg_join_keys_lookup: the LOWEST build row whose tuple equals probe row i, else 0xFFFFFFFF; build keys need not be unique.  */
+enum { AQG_JOIN_INNER = 0, AQG_JOIN_LEFT = 1, AQG_JOIN_SEMI = 2, AQG_JOIN_ANTI = 3 };
+int aqg_join_keys_count(aqg_ctx* ctx, int kind, int nkeys, const int* key_dtypes,
+                        const void* const* build_keys, uint32_t nb,
+                        const void* const* probe_keys, uint32_t np, uint64_t* m_host);
+int aqg_join_keys_pairs(aqg_ctx* ctx, int kind, int nkeys, const int* key_dtypes,
+                        const void* const* build_keys, uint32_t nb,
+                        const void* const* probe_keys, uint32_t np,
+                        uint32_t* probe_rows_out, uint32_t* build_rows_out, uint64_t capacity, uint64_t* m_host);
+int aqg_join_keys_lookup(aqg_ctx* ctx, int nkeys, const int* key_dtypes,
+                         const void* const* build_keys, uint32_t nb,
+                         const void* const* probe_keys, uint32_t np, uint32_t* build_row_of_probe);
+/* diagnostics of the last aqg_join_keys_* call on this context (like aqg_select_last_routes): the tuple form (PACKED: at most 8
+ * bytes, one 64-bit word; WIDE: compared column by column) and the table route (LDS: table and group keys copied into LDS; HBM:
+ * read in place) of its probe, the distinct build tuples G and the slots of the table (the power of two >= 2G, at least 16).
+ * All zero when the call ran no probe (an empty side, an argument error).  aqg_join_keys_lookup on ONE plain integer key runs the
+ * probe of aqg_join_lookup, whose table is over the build rows: build_groups reads 0, table_slots the power of two >= 2 nb.      */
+enum { AQG_JOIN_ROUTE_PACKED = 1, AQG_JOIN_ROUTE_WIDE = 2, AQG_JOIN_ROUTE_LDS = 4, AQG_JOIN_ROUTE_HBM = 8 };
+int aqg_join_last(aqg_ctx* ctx, uint32_t* routes, uint32_t* build_groups, uint32_t* table_slots);
+/* host, pure (like aqg_dtype_size): the first slot the kernels try for each of n tuples given as HOST columns, in a table of
+ * `table_slots` (a power of two) slots -- lets a test build collision chains without knowing the hash */
+int aqg_join_tuple_slots(int nkeys, const int* key_dtypes, const void* const* host_keys, uint32_t n, uint32_t table_slots,
+                         uint32_t* slots_out_host);
 
 /* ---- the exchange step of row-sharded group-bys -------------------------------------------------
  * Tables shard by row range, one process per GPU; every shard groups its own rows and the shards' group tables are merged
