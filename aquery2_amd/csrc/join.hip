@@ -8,16 +8,16 @@
 //   aqg_join_lookup   unique-key dimension lookup (h2o join + group-by, config 4): an open-addressing
 //                     table {key -> lowest build row} in HBM (L2-resident for small dimensions); the
 //                     probe is one coalesced pass over the fact key column.
-//   aqg_join_count / aqg_join_pairs   general inner join: group the build side (aqg_groupby_build +
-//                     postproc), look each probe key up among the distinct build keys, prefix-sum the
-//                     match counts, expand.
+//   aqg_join_count / aqg_join_pairs   general inner join: group the build side (JoinBuild: aqg_groupby_build, the row lists only
+//                     when pairs are written), look each probe key up among the distinct build keys into gid[np];
+//                     count, 64-bit total, scan and emit are aqg_join_tail's (join_tail.hip), shared with join_keys.hip.
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
+#include "join_tail.hpp"
 
 namespace {
 
 constexpr uint64_t JEMPTY = ~0ull;
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 // slot of a key in a table of 2^bits slots: 32-bit multiplies only (the probe loop is bound by VALU issue, and a 64-bit multiply
 // costs four quarter-rate 32-bit ones); the TOP bits of the product are the well-mixed ones
@@ -35,25 +35,6 @@ __device__ inline uint64_t key_bits(int dt, const void* col, size_t i) {   // si
     case AQG_UINT16: return static_cast<const uint16_t*>(col)[i];
     case AQG_UINT32: return static_cast<const uint32_t*>(col)[i];
     default: return static_cast<const uint64_t*>(col)[i];
-    }
-}
-
-template <class T> __device__ inline void key_bits4_t(const void* col, const size_t (&ix)[4], uint64_t (&k)[4]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const T v = static_cast<const T*>(col)[ix[q]];
-        if constexpr (std::is_signed_v<T>) k[q] = (uint64_t)(int64_t)v; else k[q] = (uint64_t)v;
-    }
-}
-__device__ inline void key_bits4(int dt, const void* col, const size_t (&ix)[4], uint64_t (&k)[4]) {
-    switch (dt) {
-    case AQG_INT8: key_bits4_t<int8_t>(col, ix, k); break;
-    case AQG_INT16: key_bits4_t<int16_t>(col, ix, k); break;
-    case AQG_INT32: key_bits4_t<int32_t>(col, ix, k); break;
-    case AQG_UINT8: case AQG_BOOL: key_bits4_t<uint8_t>(col, ix, k); break;
-    case AQG_UINT16: key_bits4_t<uint16_t>(col, ix, k); break;
-    case AQG_UINT32: key_bits4_t<uint32_t>(col, ix, k); break;
-    default: key_bits4_t<uint64_t>(col, ix, k); break;
     }
 }
 
@@ -150,29 +131,7 @@ __global__ void __launch_bounds__(256) jt_probe_kernel(int dt, const void* __res
     default: probe_rows<LDS>(static_cast<const uint64_t*>(col), n, t, keys, val, out); break;
     }
 }
-__global__ void __launch_bounds__(256) match_count_kernel(const uint32_t* __restrict__ gid, uint32_t np, const uint32_t* __restrict__ counts, uint32_t* __restrict__ cnt) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= np; i += gridDim.x * blockDim.x)
-        cnt[i] = (i < np && gid[i] != NONE) ? counts[gid[i]] : 0;
-}
-// 64-bit total of the per-probe-row match counts (their 32-bit exclusive scan wraps beyond 2^32 matches: 70,000 x 70,000 equal keys)
-__global__ void __launch_bounds__(256) match_total_kernel(const uint32_t* __restrict__ cnt, uint32_t np, unsigned long long* __restrict__ total) {
-    unsigned long long s = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < np; i += gridDim.x * blockDim.x) s += cnt[i];
-    s = wave_reduce(s, OpAdd{});
-    if (lane_id() == 0 && s) atomicAdd(total, s);
-}
-__global__ void __launch_bounds__(256) expand_kernel(const uint32_t* __restrict__ gid, uint32_t np, const uint32_t* __restrict__ out_off,
-                                                     const uint32_t* __restrict__ grp_off, const uint32_t* __restrict__ rows_desc,
-                                                     uint32_t* __restrict__ probe_rows, uint32_t* __restrict__ build_rows) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < np; i += gridDim.x * blockDim.x) {
-        uint32_t g = gid[i];
-        if (g == NONE) continue;
-        uint32_t b = grp_off[g], e = grp_off[g + 1], o = out_off[i];
-        for (uint32_t t = 0; t < e - b; ++t) { probe_rows[o + t] = i; build_rows[o + t] = rows_desc[e - 1 - t]; }   // ascending build rows
-    }
-}
 
-uint32_t pow2_at_least(uint64_t v) { uint64_t p = 16; while (p < v) p <<= 1; return (uint32_t)p; }
 bool key_dtype_ok(int t) {
     switch (t) { case AQG_INT8: case AQG_INT16: case AQG_INT32: case AQG_INT64: case AQG_UINT8: case AQG_UINT16: case AQG_UINT32: case AQG_UINT64: case AQG_BOOL: return true; }
     return false;
@@ -190,13 +149,19 @@ int make_table(aqg_ctx* ctx, int t, const void* col, uint32_t n, JTable* jt) {
     return aqg_check_launch(ctx, "jt_build_kernel");
 }
 
-void launch_probe(aqg_ctx* ctx, int t, const void* pk, uint32_t np, const JTable& jt, uint32_t* out) {
+// make_table's share of the workspace: keys, then payloads with the sentinel's behind them, each aligned to 256 bytes
+size_t table_bytes(uint32_t n) { return (size_t)pow2_at_least((uint64_t)n * 2) * 12 + 4 + 2 * 256; }
+
+// returns whether the LDS route ran
+bool launch_probe(aqg_ctx* ctx, int t, const void* pk, uint32_t np, const JTable& jt, uint32_t* out) {
     const size_t lds = (size_t)jt.cap * 12;
-    if (lds <= 48 * 1024 && np >= (1u << 16)) {
+    const bool use_lds = join_lds_route(lds, np);
+    if (use_lds) {
         hipLaunchKernelGGL((jt_probe_kernel<true>), dim3(aqg_grid(ctx, np / 4 + 1, 256, 2, lds <= 20 * 1024 ? 8 : 3)), dim3(256), lds, ctx->stream, t, pk, np, jt, out);
     } else {
         hipLaunchKernelGGL((jt_probe_kernel<false>), dim3(aqg_grid(ctx, np / 4 + 1, 256, 2, 8)), dim3(256), 0, ctx->stream, t, pk, np, jt, out);
     }
+    return use_lds;
 }
 
 int join_core(aqg_ctx* ctx, int t, const void* bk, uint32_t nb, const void* pk, uint32_t np, uint32_t* probe_rows, uint32_t* build_rows,
@@ -206,75 +171,49 @@ int join_core(aqg_ctx* ctx, int t, const void* bk, uint32_t nb, const void* pk, 
     AQG_CHECK_ROWS(ctx, nb, "join");
     AQG_CHECK_ROWS(ctx, np, "join");
     if (nb == 0 || np == 0) return AQG_OK;
-    // 1. group the build side (dense ids, counts, descending row lists)
-    aqg_groupby* gb = nullptr;
-    const void* kcols[1] = {bk};
-    AQG_TRY(aqg_groupby_build(ctx, 1, &t, kcols, nb, 0, &gb));
-    const uint32_t G = aqg_groupby_ngroups(gb);
-    uint32_t *grp_off = nullptr, *rows_desc = nullptr;
-    void* dkeys = nullptr;
-    int rc = aqg_malloc(ctx, ((size_t)G + 1) * 4, (void**)&grp_off);
-    if (rc == AQG_OK) rc = aqg_malloc(ctx, (size_t)nb * 4, (void**)&rows_desc);
-    if (rc == AQG_OK) rc = aqg_malloc(ctx, (size_t)G * 8, &dkeys);
-    if (rc == AQG_OK) rc = aqg_groupby_postproc(gb, grp_off, rows_desc);
-    if (rc == AQG_OK) rc = aqg_groupby_keys(gb, 0, dkeys);
-    auto cleanup = [&]() { aqg_free(ctx, grp_off); aqg_free(ctx, rows_desc); aqg_free(ctx, dkeys); aqg_groupby_destroy(gb); };
-    if (rc != AQG_OK) { cleanup(); return rc; }
+    if (!build_rows) probe_rows = nullptr;             // pairs are written into both outputs or not at all
+    // 1. group the build side (dense ids, counts, distinct keys; descending row lists for the pairs)
+    JoinBuild build(ctx);
+    AQG_TRY(build.setup(1, &t, &bk, nb, probe_rows != nullptr));
+    AQG_TRY(build.keys0());
     // 2. distinct build key -> group id, probe
-    rc = aqg_ws_reset(ctx);
-    size_t need = (size_t)pow2_at_least((uint64_t)G * 2) * 12 + ((size_t)np + 1) * 8 + (((size_t)np + 1) / 2048 + 2) * 4 + 16384 + 256;
-    if (rc == AQG_OK) rc = aqg_ws_ensure(ctx, need);
+    AQG_TRY(aqg_ws_reset(ctx));
+    AQG_TRY(aqg_ws_ensure(ctx, table_bytes(build.G) + (size_t)np * 4 + 256 + aqg_join_tail_ws_bytes(np)));
     JTable jt;
-    uint32_t *gid = nullptr, *cnt = nullptr, *bsum = nullptr;
-    unsigned long long* total = nullptr;
-    if (rc == AQG_OK) rc = make_table(ctx, t, dkeys, G, &jt);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, 1, &total);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, (size_t)np + 1, &gid);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, (size_t)np + 1, &cnt);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, ((size_t)np + 1) / 2048 + 2, &bsum);
-    if (rc != AQG_OK) { cleanup(); return rc; }
-    unsigned pg = aqg_grid(ctx, np, 256, 4, 8);
+    uint32_t* gid = nullptr;
+    AQG_TRY(make_table(ctx, t, build.dkeys, build.G, &jt));
+    AQG_TRY(aqg_ws_get(ctx, (size_t)np, &gid));
     launch_probe(ctx, t, pk, np, jt, gid);
-    hipLaunchKernelGGL(match_count_kernel, dim3(pg), dim3(256), 0, ctx->stream, gid, np, aqg_groupby_counts(gb), cnt);
-    // the number of matches in 64 bits, BEFORE the 32-bit offsets are trusted: with duplicate keys it passes 2^32 at small inputs
-    rc = hipMemsetAsync(total, 0, 8, ctx->stream) == hipSuccess ? AQG_OK : AQG_ERR_HIP;
-    if (rc == AQG_OK) hipLaunchKernelGGL(match_total_kernel, dim3(pg), dim3(256), 0, ctx->stream, (const uint32_t*)cnt, np, total);
-    unsigned long long m64 = 0;
-    if (rc == AQG_OK) rc = aqg_d2h(ctx, &m64, total, 8);
-    if (rc != AQG_OK) { cleanup(); return rc; }
-    *m_host = m64;
-    if (probe_rows && build_rows && m64) {
-        // pairs are addressed by uint32 offsets like every row index of this library
-        if (m64 > (unsigned long long)AQG_MAX_ROWS) { cleanup(); return aqg_fail(ctx, AQG_ERR_OVERFLOW, "aqg_join_pairs: more than AQG_MAX_ROWS matching pairs (*m_host holds the count)"); }
-        if (capacity < m64) { cleanup(); return aqg_fail(ctx, AQG_ERR_OVERFLOW, "aqg_join_pairs: output capacity too small"); }
-        rc = aqg_exclusive_scan_u32(ctx, cnt, (uint64_t)np + 1, bsum);
-        if (rc != AQG_OK) { cleanup(); return rc; }
-        hipLaunchKernelGGL(expand_kernel, dim3(pg), dim3(256), 0, ctx->stream, gid, np, cnt, grp_off, rows_desc, probe_rows, build_rows);
-        rc = aqg_check_launch(ctx, "expand_kernel");
-        if (rc == AQG_OK) rc = aqg_sync(ctx);
-    }
-    cleanup();
-    return rc;
+    AQG_TRY(aqg_check_launch(ctx, "jt_probe_kernel"));
+    // 3. count, total, scan, emit
+    return aqg_join_tail(ctx, AQG_JOIN_INNER, gid, np, build, probe_rows, build_rows, capacity, m_host, "aqg_join_pairs");
 }
 
 } // namespace
 
-extern "C" {
-
-int aqg_join_lookup(aqg_ctx* ctx, int t, const void* bk, uint32_t nb, const void* pk, uint32_t np, uint32_t* out) {
+int aqg_join_lookup_routed(aqg_ctx* ctx, int t, const void* bk, uint32_t nb, const void* pk, uint32_t np, uint32_t* out, uint32_t* table_slots, bool* lds) {
     if (!ctx || (!bk && nb) || (!pk && np) || (!out && np)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_lookup: bad argument");
     if (!key_dtype_ok(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_join_lookup: integer key columns only");
     AQG_CHECK_ROWS(ctx, nb, "aqg_join_lookup");
     AQG_CHECK_ROWS(ctx, np, "aqg_join_lookup");
     if (np == 0) return AQG_OK;
     AQG_TRY(aqg_ws_reset(ctx));
-    AQG_TRY(aqg_ws_ensure(ctx, (size_t)pow2_at_least((uint64_t)nb * 2) * 12 + 8192));
+    AQG_TRY(aqg_ws_ensure(ctx, table_bytes(nb)));
     JTable jt;
     AQG_TRY(make_table(ctx, t, bk, nb, &jt));
     aqg_kernel_timer_begin(ctx);
-    launch_probe(ctx, t, pk, np, jt, out);
+    *lds = launch_probe(ctx, t, pk, np, jt, out);
     aqg_kernel_timer_end(ctx);
+    *table_slots = jt.cap;
     return aqg_check_launch(ctx, "jt_probe_kernel");
+}
+
+extern "C" {
+
+int aqg_join_lookup(aqg_ctx* ctx, int t, const void* bk, uint32_t nb, const void* pk, uint32_t np, uint32_t* out) {
+    uint32_t slots = 0;
+    bool lds = false;
+    return aqg_join_lookup_routed(ctx, t, bk, nb, pk, np, out, &slots, &lds);
 }
 
 int aqg_join_count(aqg_ctx* ctx, int t, const void* bk, uint32_t nb, const void* pk, uint32_t np, uint64_t* m_host) {

@@ -11,18 +11,16 @@
 //           registers, the first slot of all four rows read before the first compare, one 16-byte store of {group id | NONE}
 //           (or of the group's first row: aqg_join_keys_lookup).  PACKED: the tuple is one 64-bit word; WIDE: up to eight.
 //           LDS: table and group keys copied into LDS first (small dimensions under large fact sides); HBM: read in place.
-//   after   per-row output counts -> 64-bit total (copied to the host before 32-bit offsets are trusted) -> exclusive scan -> emit.
+//   after   aqg_join_tail (join_tail.hip, shared with join.hip): per-row output counts -> 64-bit total -> exclusive scan -> emit.
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
 #include "join_keys.hpp"
+#include "join_tail.hpp"
 
 namespace {
 
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint64_t SLOT_EMPTY = ~0ull;
 constexpr int JR = 4;                                  // consecutive rows per lane
-constexpr size_t JK_LDS_LIMIT = 48 * 1024;             // join.hip's rule, kept: table + group keys within 48 KB and >= 2^16 probe rows
-constexpr uint32_t JK_LDS_MIN_ROWS = 1u << 16;
 
 struct JKTable { uint64_t* slots; uint64_t* gkeys; uint32_t cap, G; };      // gkeys: [nw][G] words (PACKED: [G])
 
@@ -168,47 +166,7 @@ __global__ void __launch_bounds__(256) jk_probe_kernel(JKCols kc, uint32_t n, JK
     }
 }
 
-// rows of output per probe row: INNER c, LEFT max(c, 1), SEMI c > 0, ANTI c == 0   (cnt[np] = 0: the scan's total slot)
-__global__ void __launch_bounds__(256) jk_count_kernel(int kind, const uint32_t* __restrict__ gid, uint32_t np, const uint32_t* __restrict__ counts, uint32_t* __restrict__ cnt) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= np; i += gridDim.x * blockDim.x) {
-        uint32_t c = 0;
-        if (i < np) {
-            const uint32_t g = gid[i];
-            switch (kind) {
-            case AQG_JOIN_INNER: c = g != NONE ? counts[g] : 0u; break;
-            case AQG_JOIN_LEFT: c = g != NONE ? counts[g] : 1u; break;
-            case AQG_JOIN_SEMI: c = g != NONE; break;
-            default: c = g == NONE; break;
-            }
-        }
-        cnt[i] = c;
-    }
-}
-__global__ void __launch_bounds__(256) jk_total_kernel(const uint32_t* __restrict__ cnt, uint32_t np, unsigned long long* __restrict__ total) {
-    unsigned long long s = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < np; i += gridDim.x * blockDim.x) s += cnt[i];
-    s = wave_reduce(s, OpAdd{});
-    if (lane_id() == 0 && s) atomicAdd(total, s);
-}
-__global__ void __launch_bounds__(256) jk_emit_kernel(int kind, const uint32_t* __restrict__ gid, uint32_t np, const uint32_t* __restrict__ out_off,
-                                                      const uint32_t* __restrict__ grp_off, const uint32_t* __restrict__ rows_desc,
-                                                      uint32_t* __restrict__ probe_rows, uint32_t* __restrict__ build_rows) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < np; i += gridDim.x * blockDim.x) {
-        const uint32_t g = gid[i], o = out_off[i];
-        if (kind == AQG_JOIN_SEMI) { if (g != NONE) probe_rows[o] = i; continue; }
-        if (kind == AQG_JOIN_ANTI) { if (g == NONE) probe_rows[o] = i; continue; }
-        if (g == NONE) {
-            if (kind == AQG_JOIN_LEFT) { probe_rows[o] = i; build_rows[o] = NONE; }
-            continue;
-        }
-        const uint32_t b = grp_off[g], e = grp_off[g + 1];
-        for (uint32_t t = 0; t < e - b; ++t) { probe_rows[o + t] = i; build_rows[o + t] = rows_desc[e - 1 - t]; }   // ascending build rows
-    }
-}
-
-uint32_t pow2_at_least(uint64_t v) { uint64_t p = 16; while (p < v) p <<= 1; return (uint32_t)p; }
-
-int check_args(aqg_ctx* ctx, const char* who, int nkeys, const int* dts, const void* const* bk, uint32_t nb, const void* const* pk, uint32_t np, JKCols* kb, JKCols* kp) {
+int check_args(aqg_ctx* ctx, int nkeys, const int* dts, const void* const* bk, uint32_t nb, const void* const* pk, uint32_t np, JKCols* kb, JKCols* kp) {
     if (!ctx || !dts || !bk || !pk || nkeys < 1 || nkeys > JK_MAXW) return aqg_fail(ctx, AQG_ERR_ARG, "join keys: bad argument (1..8 key columns)");
     int rc = jk_plan(nkeys, dts, bk, kb);
     if (rc == AQG_OK) rc = jk_plan(nkeys, dts, pk, kp);
@@ -237,7 +195,7 @@ int launch_probe(aqg_ctx* ctx, const JKCols& kp, uint32_t np, const JKTable& t, 
     int aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     for (int c = 0; c < kp.nw; ++c) aligned = aligned && (reinterpret_cast<uintptr_t>(kp.col[c]) & 15) == 0;
     const size_t lds = (size_t)t.cap * 8 + (size_t)(kp.packed ? 1 : kp.nw) * t.G * 8;
-    const bool use_lds = lds <= JK_LDS_LIMIT && np >= JK_LDS_MIN_ROWS;
+    const bool use_lds = join_lds_route(lds, np);
     ctx->join_routes = (kp.packed ? AQG_JOIN_ROUTE_PACKED : AQG_JOIN_ROUTE_WIDE) | (use_lds ? AQG_JOIN_ROUTE_LDS : AQG_JOIN_ROUTE_HBM);
     ctx->join_groups = t.G;
     ctx->join_slots = t.cap;
@@ -250,70 +208,30 @@ int launch_probe(aqg_ctx* ctx, const JKCols& kp, uint32_t np, const JKTable& t, 
     return aqg_check_launch(ctx, "jk_probe_kernel");
 }
 
-int join_keys_core(aqg_ctx* ctx, const char* who, int kind, int nkeys, const int* dts, const void* const* bk, uint32_t nb, const void* const* pk, uint32_t np,
+int join_keys_core(aqg_ctx* ctx, int kind, int nkeys, const int* dts, const void* const* bk, uint32_t nb, const void* const* pk, uint32_t np,
                    uint32_t* probe_rows, uint32_t* build_rows, uint64_t capacity, uint64_t* m_host) {
     if (m_host) *m_host = 0;
     JKCols kb, kp;
-    AQG_TRY(check_args(ctx, who, nkeys, dts, bk, nb, pk, np, &kb, &kp));
+    AQG_TRY(check_args(ctx, nkeys, dts, bk, nb, pk, np, &kb, &kp));
     if (!m_host || kind < AQG_JOIN_INNER || kind > AQG_JOIN_ANTI) return aqg_fail(ctx, AQG_ERR_ARG, "join keys: bad argument (kind, m_host)");
     const bool with_build_rows = kind == AQG_JOIN_INNER || kind == AQG_JOIN_LEFT;
     if (probe_rows && with_build_rows && !build_rows) return aqg_fail(ctx, AQG_ERR_ARG, "join keys: build_rows_out is NULL");
     ctx->join_routes = ctx->join_groups = ctx->join_slots = 0;
     if (np == 0) return AQG_OK;
     // 1. group the build side (dense ids, counts, descending row lists); an empty one leaves every probe row without a partner
-    aqg_groupby* gb = nullptr;
-    uint32_t *grp_off = nullptr, *rows_desc = nullptr;
-    auto cleanup = [&]() { aqg_free(ctx, grp_off); aqg_free(ctx, rows_desc); if (gb) aqg_groupby_destroy(gb); };
-    int rc = AQG_OK;
-    uint32_t G = 0;
-    if (nb) {
-        AQG_TRY(aqg_groupby_build(ctx, nkeys, dts, bk, nb, 0, &gb));
-        G = aqg_groupby_ngroups(gb);
-        if (with_build_rows && probe_rows) {
-            rc = aqg_malloc(ctx, ((size_t)G + 1) * 4, (void**)&grp_off);
-            if (rc == AQG_OK) rc = aqg_malloc(ctx, (size_t)nb * 4, (void**)&rows_desc);
-            if (rc == AQG_OK) rc = aqg_groupby_postproc(gb, grp_off, rows_desc);
-            if (rc != AQG_OK) { cleanup(); return rc; }
-        }
-    }
+    JoinBuild build(ctx);
+    if (nb) AQG_TRY(build.setup(nkeys, dts, bk, nb, with_build_rows && probe_rows));
     // 2. table over the distinct build tuples, probe
-    rc = aqg_ws_reset(ctx);
-    if (rc == AQG_OK) rc = aqg_ws_ensure(ctx, table_bytes(kb, G) + ((size_t)np + 4) * 8 + (((size_t)np + 1) / 2048 + 2) * 4 + 16384 + 256);
+    AQG_TRY(aqg_ws_reset(ctx));
+    AQG_TRY(aqg_ws_ensure(ctx, table_bytes(kb, build.G) + (size_t)np * 4 + 256 + aqg_join_tail_ws_bytes(np)));
     JKTable t{};
-    uint32_t *gid = nullptr, *cnt = nullptr, *bsum = nullptr;
-    unsigned long long* total = nullptr;
-    if (rc == AQG_OK && nb) rc = make_table(ctx, kb, gb, &t);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, 2, &total);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, (size_t)np + 4, &gid);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, (size_t)np + 4, &cnt);
-    if (rc == AQG_OK) rc = aqg_ws_get(ctx, ((size_t)np + 1) / 2048 + 2, &bsum);
-    if (rc != AQG_OK) { cleanup(); return rc; }
-    const unsigned pg = aqg_grid(ctx, np, 256, 4, 8);
-    if (nb) rc = launch_probe(ctx, kp, np, t, nullptr, gid);
-    else rc = hipMemsetAsync(gid, 0xFF, (size_t)np * 4, ctx->stream) == hipSuccess ? AQG_OK : AQG_ERR_HIP;
-    if (rc != AQG_OK) { cleanup(); return rc; }
-    hipLaunchKernelGGL(jk_count_kernel, dim3(pg), dim3(256), 0, ctx->stream, kind, (const uint32_t*)gid, np, nb ? aqg_groupby_counts(gb) : (const uint32_t*)nullptr, cnt);
-    // the number of output rows in 64 bits, BEFORE the 32-bit offsets are trusted: with duplicate tuples it passes 2^32 at small inputs
-    rc = hipMemsetAsync(total, 0, 8, ctx->stream) == hipSuccess ? AQG_OK : AQG_ERR_HIP;
-    if (rc == AQG_OK) hipLaunchKernelGGL(jk_total_kernel, dim3(pg), dim3(256), 0, ctx->stream, (const uint32_t*)cnt, np, total);
-    unsigned long long m64 = 0;
-    if (rc == AQG_OK) rc = aqg_check_launch(ctx, "jk_total_kernel");
-    if (rc == AQG_OK) rc = aqg_d2h(ctx, &m64, total, 8);
-    if (rc != AQG_OK) { cleanup(); return rc; }
-    *m_host = m64;
-    if (probe_rows && m64) {
-        // output rows are addressed by uint32 offsets like every row index of this library
-        if (m64 > (unsigned long long)AQG_MAX_ROWS) { cleanup(); return aqg_fail(ctx, AQG_ERR_OVERFLOW, "aqg_join_keys_pairs: more than AQG_MAX_ROWS output rows (*m_host holds the count)"); }
-        if (capacity < m64) { cleanup(); return aqg_fail(ctx, AQG_ERR_OVERFLOW, "aqg_join_keys_pairs: output capacity too small (*m_host holds the count)"); }
-        rc = aqg_exclusive_scan_u32(ctx, cnt, (uint64_t)np + 1, bsum);
-        if (rc != AQG_OK) { cleanup(); return rc; }
-        hipLaunchKernelGGL(jk_emit_kernel, dim3(pg), dim3(256), 0, ctx->stream, kind, (const uint32_t*)gid, np, (const uint32_t*)cnt, (const uint32_t*)grp_off,
-                           (const uint32_t*)rows_desc, probe_rows, build_rows);
-        rc = aqg_check_launch(ctx, "jk_emit_kernel");
-        if (rc == AQG_OK) rc = aqg_sync(ctx);
-    }
-    cleanup();
-    return rc;
+    uint32_t* gid = nullptr;
+    if (nb) AQG_TRY(make_table(ctx, kb, build.gb, &t));
+    AQG_TRY(aqg_ws_get(ctx, (size_t)np, &gid));
+    if (nb) AQG_TRY(launch_probe(ctx, kp, np, t, nullptr, gid));
+    else AQG_HIP(ctx, hipMemsetAsync(gid, 0xFF, (size_t)np * 4, ctx->stream));
+    // 3. count, total, scan, emit
+    return aqg_join_tail(ctx, kind, gid, np, build, probe_rows, build_rows, capacity, m_host, "aqg_join_keys_pairs");
 }
 
 } // namespace
@@ -322,18 +240,18 @@ extern "C" {
 
 int aqg_join_keys_count(aqg_ctx* ctx, int kind, int nkeys, const int* key_dtypes, const void* const* build_keys, uint32_t nb,
                         const void* const* probe_keys, uint32_t np, uint64_t* m_host) {
-    return join_keys_core(ctx, "aqg_join_keys_count", kind, nkeys, key_dtypes, build_keys, nb, probe_keys, np, nullptr, nullptr, 0, m_host);
+    return join_keys_core(ctx, kind, nkeys, key_dtypes, build_keys, nb, probe_keys, np, nullptr, nullptr, 0, m_host);
 }
 
 int aqg_join_keys_pairs(aqg_ctx* ctx, int kind, int nkeys, const int* key_dtypes, const void* const* build_keys, uint32_t nb,
                         const void* const* probe_keys, uint32_t np, uint32_t* probe_rows_out, uint32_t* build_rows_out, uint64_t capacity, uint64_t* m_host) {
-    return join_keys_core(ctx, "aqg_join_keys_pairs", kind, nkeys, key_dtypes, build_keys, nb, probe_keys, np, probe_rows_out, build_rows_out, capacity, m_host);
+    return join_keys_core(ctx, kind, nkeys, key_dtypes, build_keys, nb, probe_keys, np, probe_rows_out, build_rows_out, capacity, m_host);
 }
 
 int aqg_join_keys_lookup(aqg_ctx* ctx, int nkeys, const int* key_dtypes, const void* const* build_keys, uint32_t nb,
                          const void* const* probe_keys, uint32_t np, uint32_t* out) {
     JKCols kb, kp;
-    AQG_TRY(check_args(ctx, "aqg_join_keys_lookup", nkeys, key_dtypes, build_keys, nb, probe_keys, np, &kb, &kp));
+    AQG_TRY(check_args(ctx, nkeys, key_dtypes, build_keys, nb, probe_keys, np, &kb, &kp));
     if (!out && np) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_keys_lookup: bad argument");
     ctx->join_routes = ctx->join_groups = ctx->join_slots = 0;
     if (np == 0) return AQG_OK;
@@ -341,26 +259,24 @@ int aqg_join_keys_lookup(aqg_ctx* ctx, int nkeys, const int* key_dtypes, const v
     if (nkeys == 1 && kb.kind[0] <= JK_U64 && key_dtypes[0] != AQG_DATE) {
         // One plain integer key: the probe of join.hip answers the same question (lowest row, NONE) without grouping the build side, and
         // measured 1.67 ms against 4.72 ms for the tuple probe at 1e9 rows under a 100-row dimension.  The table
-        // is over the build ROWS there: build_groups reads 0.
-        const uint32_t cap = pow2_at_least((uint64_t)nb * 2);
-        ctx->join_routes = AQG_JOIN_ROUTE_PACKED | ((size_t)cap * 12 <= JK_LDS_LIMIT && np >= JK_LDS_MIN_ROWS ? AQG_JOIN_ROUTE_LDS : AQG_JOIN_ROUTE_HBM);
-        ctx->join_slots = cap;
-        return aqg_join_lookup(ctx, key_dtypes[0], build_keys[0], nb, probe_keys[0], np, out);
+        // is over the build ROWS there: build_groups reads 0, slots and route are what that probe reports.
+        uint32_t slots = 0;
+        bool lds = false;
+        AQG_TRY(aqg_join_lookup_routed(ctx, key_dtypes[0], build_keys[0], nb, probe_keys[0], np, out, &slots, &lds));
+        ctx->join_routes = AQG_JOIN_ROUTE_PACKED | (lds ? AQG_JOIN_ROUTE_LDS : AQG_JOIN_ROUTE_HBM);
+        ctx->join_slots = slots;
+        return AQG_OK;
     }
-    aqg_groupby* gb = nullptr;
-    AQG_TRY(aqg_groupby_build(ctx, nkeys, key_dtypes, build_keys, nb, 0, &gb));
-    int rc = aqg_ws_reset(ctx);
-    if (rc == AQG_OK) rc = aqg_ws_ensure(ctx, table_bytes(kb, aqg_groupby_ngroups(gb)) + 8192);
+    JoinBuild build(ctx);
+    AQG_TRY(build.setup(nkeys, key_dtypes, build_keys, nb, false));
+    AQG_TRY(aqg_ws_reset(ctx));
+    AQG_TRY(aqg_ws_ensure(ctx, table_bytes(kb, build.G)));
     JKTable t{};
-    if (rc == AQG_OK) rc = make_table(ctx, kb, gb, &t);
-    if (rc == AQG_OK) {
-        aqg_kernel_timer_begin(ctx);
-        rc = launch_probe(ctx, kp, np, t, aqg_groupby_first_rows(gb), out);
-        aqg_kernel_timer_end(ctx);
-    }
-    if (rc == AQG_OK) rc = aqg_sync(ctx);              // the probe reads the handle's first rows
-    aqg_groupby_destroy(gb);
-    return rc;
+    AQG_TRY(make_table(ctx, kb, build.gb, &t));
+    aqg_kernel_timer_begin(ctx);
+    const int rc = launch_probe(ctx, kp, np, t, aqg_groupby_first_rows(build.gb), out);
+    aqg_kernel_timer_end(ctx);
+    return rc == AQG_OK ? aqg_sync(ctx) : rc;          // the probe reads the handle's first rows
 }
 
 int aqg_join_last(aqg_ctx* ctx, uint32_t* routes, uint32_t* build_groups, uint32_t* table_slots) {

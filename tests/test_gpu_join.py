@@ -255,6 +255,47 @@ def raw_pairs(gpu, bd, pd, out_p, out_b, capacity):
     return rc, m.value
 
 
+def _count_int16_duplicates(rng):
+    return rng.integers(0, 40, 500).astype(np.int16), rng.integers(-5, 45, 2000).astype(np.int16)
+
+
+def _count_all_ones_int64(rng):
+    build = rng.choice(distinct_keys(rng, np.int64, 900, exclude=(-1,)), 3000)
+    probe = mixed_probe(rng, build, 5003, np.int64)
+    build[[2999, 1500, 12]] = -1
+    probe[[0, 2500, 5002]] = -1
+    return build, probe
+
+
+def _count_hashed_build(rng):
+    build = distinct_keys(rng, np.int32, 200_000)[rng.integers(0, 200_000, 300_000)]
+    return build, mixed_probe(rng, build, 100_003, np.int32)
+
+
+COUNT_CASES = {"int16_duplicates": _count_int16_duplicates, "all_ones_int64": _count_all_ones_int64, "hashed_build": _count_hashed_build}
+
+
+@pytest.mark.parametrize("name", list(COUNT_CASES))
+def test_count_without_pairs(gpu, name):
+    """aqg_join_count builds no row lists (no aqg_groupby_postproc): its count is the model's and the m_host of aqg_join_pairs on the same
+    columns, and the context it leaves behind still groups -- no handle or buffer of the count-only call is left in the way"""
+    rng = np.random.default_rng(50)
+    build, probe = COUNT_CASES[name](rng)
+    gk, gv = rng.integers(0, 50, 100_000).astype(np.int32), rng.integers(-1000, 1000, 100_000).astype(np.int32)
+    bd, pd = gpu.to_device(build), gpu.to_device(probe)
+    want = jm.count(build, probe)
+    assert want > 0 and gpu.join_count(bd, pd) == want
+    gb = gpu.groupby_agg([gk], [ck.RED_SUM], [gv])
+    keys, first = np.unique(gk, return_index=True)
+    by_first = np.argsort(first)
+    assert gb.keys(0, np.int32).tolist() == keys[by_first].tolist() and gb.first_rows().tolist() == first[by_first].tolist()
+    assert ck.i128_to_int(gb.result(0, ck.RED_SUM, ck.INT32)) == [int(gv[gk == k].sum()) for k in keys[by_first]]
+    gb.destroy()
+    op, ob = gpu.empty(want, np.uint32), gpu.empty(want, np.uint32)
+    assert raw_pairs(gpu, bd, pd, op, ob, want) == (AQG_OK, want)
+    assert gpu.join_count(bd, pd) == want
+
+
 def test_join_returns(gpu, oracle):
     rng = np.random.default_rng(39)
     # a group-by and a join to be repeated at the end, on the same context

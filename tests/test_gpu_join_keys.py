@@ -353,6 +353,21 @@ def test_one_integer_key_equals_the_integer_joins(gpu, dt):
         assert np.array_equal(gpu.join_keys_lookup([build], [probe]), gpu.join_lookup(build, probe))
 
 
+@pytest.mark.parametrize("nb,npr,route,slots", [(2048, 65_536, LDS, 4096), (2049, 65_536, HBM, 8192), (2048, 65_535, HBM, 4096)],
+                         ids=["48KB_table_2^16_rows", "one_build_row_more", "one_probe_row_fewer"])
+def test_one_int32_key_lookup_reports_the_route_it_ran(gpu, nb, npr, route, slots):
+    """aqg_join_keys_lookup on one plain integer key runs join.hip's probe, and aqg_join_last says what THAT launcher decided: the edges
+    of the LDS rule (a table of 12-byte slots within 48 KB under at least 2^16 probe rows).  No other test reads the route of this path."""
+    rng = np.random.default_rng(82)
+    build = rng.permutation((np.arange(nb, dtype=np.int64) * 1_000_003 - 2**31).astype(np.int32))
+    probe = rng.integers(-2**31, 2**31, npr).astype(np.int32)
+    hit = rng.random(npr) < 0.67
+    probe[hit] = build[rng.integers(0, nb, int(hit.sum()))]
+    got = gpu.join_keys_lookup([build], [probe])
+    assert gpu.join_last() == (PACKED | route, 0, slots)
+    assert np.array_equal(got, jm.lookup(build, probe))
+
+
 # ---- limits and errors -------------------------------------------------------------------------------------------------------------
 def test_counts_beyond_32_bits_and_overflow(gpu):
     n = 70_000

@@ -1,6 +1,6 @@
 """The joins on composite and typed keys at size: ms per call of the shapes of DESIGN.md section 4.10, one JSON line per shape and call.
 
-    python tools/join_probe.py [--n 1e9] [--shapes 1,2,3,4] [--reps 5]
+    python tools/join_probe.py [--n 1e9] [--shapes 1,2,3,4,5] [--reps 5]
 
 Shapes (fact columns from aqg_gen_column, n rows; every fact row has a partner):
   1  one 4-byte key (id1), a 100-row dimension: aqg_join_keys_lookup beside aqg_join_lookup (the parent's entry), then
@@ -10,6 +10,9 @@ Shapes (fact columns from aqg_gen_column, n rows; every fact row has a partner):
      id of a fact row is its dimension row)
   3  (int64 id4, id5) on the same shape -- the WIDE form
   4  aqg_gather_fill beside aqg_gather on the full index of shape 1 (a 4-byte value column of the dimension)
+  5  the one-key joins behind their probe: one 4-byte key, n / 1000 build rows of distinct keys, n / 10 probe rows that each match once
+     (10^6 and 10^8 at the default n): aqg_join_count, aqg_join_pairs into preallocated outputs, aqg_join_keys_pairs INNER on the
+     same columns into outputs of its own (`m` and the checksum of the build rows must agree)
 ms: HIP events around the whole call (aqg_timer_start / aqg_timer_stop_ms), the median of --reps timed calls after one warm-up call;
 `times_ms` carries every call, so the spread is on the line.  `kernel_ms` is the probe kernel alone (aqg_last_kernel_ms) where the call
 records one.  `rows_per_s` and `roofline` (the share of 8 TB/s) count algorithmic bytes: the probe key bytes plus 4 per row.
@@ -60,7 +63,7 @@ def keys_lookup(d, bd, pd, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=float, default=1e9)
-    ap.add_argument("--shapes", default="1,2,3,4")
+    ap.add_argument("--shapes", default="1,2,3,4,5")
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
     n, d = int(a.n), A.Device(0)
@@ -135,6 +138,25 @@ def main():
         line(s, "aqg_groupby_build over the concatenation", n, kb, t, groups=state["gb"].ngroups, checksum=prefix_sum(d, rev, n))
         state["gb"].destroy()
         for b in cat + bd:
+            b.free()
+    if 5 in shapes:
+        nb5, np5 = max(n // 1000, 1), max(n // 10, 1)
+        fk = d.gen_column(GEN_ID1, 42, 0, np5, np5, nb5)
+        dim = d.to_device(np.random.default_rng(5).permutation(np.arange(1, nb5 + 1, dtype=np.int32)))
+        outs = [(d.empty(np5, np.uint32), d.empty(np5, np.uint32)) for _ in range(2)]
+        _, dts, bp = d._keyargs([dim])
+        _, _, pp = d._keyargs([fk])
+        m = C.c_uint64()
+        one = (d.ctx, dim.tag, C.c_void_p(dim.ptr), C.c_uint32(nb5), C.c_void_p(fk.ptr), C.c_uint32(np5))
+        (pr, br), (kpr, kbr) = outs
+        calls = (("aqg_join_count", None, lambda: d._chk(d.lib.aqg_join_count(*one, C.byref(m)), "aqg_join_count")),
+                 ("aqg_join_pairs", br, lambda: d._chk(d.lib.aqg_join_pairs(*one, C.c_void_p(pr.ptr), C.c_void_p(br.ptr), C.c_uint64(np5), C.byref(m)), "aqg_join_pairs")),
+                 ("aqg_join_keys_pairs INNER", kbr, lambda: d._chk(d.lib.aqg_join_keys_pairs(d.ctx, capi.JOIN_INNER, 1, dts, bp, nb5, pp, np5, kpr.ptr, kbr.ptr, np5, C.byref(m)),
+                                                                    "aqg_join_keys_pairs")))
+        for name, rows, f in calls:
+            t = timed(d, a.reps, f)
+            line(5, name, np5, 4, t, build_rows=nb5, m=m.value, **({} if rows is None else {"checksum": prefix_sum(d, rows.ptr, np5)}))
+        for b in (fk, dim, pr, br, kpr, kbr):
             b.free()
     d.close()
 
