@@ -95,6 +95,7 @@ template <class T> __device__ __noinline__ void store_minmax(void* out, uint32_t
         double d = unmap_f(mapped);
         v = (T)d;
         if (is_max) { T seed = dlimits<T>::min(); v = seed > v ? seed : v; }   // max seeds with numeric_limits<T>::min() (D8)
+        else { T seed = dlimits<T>::max(); v = seed < v ? seed : v; }          // min seeds with max(): a +Inf group comes out as max()
     } else if constexpr (std::is_unsigned_v<T>) v = (T)mapped;
     else v = (T)unmap_i(mapped);
     static_cast<T*>(out)[g] = v;

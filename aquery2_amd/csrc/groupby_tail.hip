@@ -203,9 +203,11 @@ __device__ inline void emit_record_from(const R& rec, uint32_t g, const EmitSpec
         uint64_t v0 = a.acc0 >= 0 ? rec.acc(a.acc0) : 0;
         const bool wide = a.dt == AQG_INT64 || a.dt == AQG_UINT64;
         // exact 128-bit sum (and sum of squares) of an integer column
-        auto sum128 = [&](int lo_acc, int hi_acc) -> aqg_i128 {
+        // (squares of a uint16 column: `x * x` is an int product that wraps negative from 46341 on, and the reference adds it SIGN-extended to
+        // its 128-bit sum; the 64-bit accumulator holds the exact signed sum of those products: extended the same way, as aqg_reduce does)
+        auto sum128 = [&](int lo_acc, int hi_acc, bool squares = false) -> aqg_i128 {
             uint64_t lo = rec.acc(lo_acc);
-            if (!wide) return vc == VC_U ? i128_from_u64(lo) : i128_from_i64((int64_t)lo);
+            if (!wide) return vc == VC_U && !(squares && a.dt == AQG_UINT16) ? i128_from_u64(lo) : i128_from_i64((int64_t)lo);
             uint64_t hi = rec.acc(hi_acc);                       // sum of the high halves, to be shifted by 32
             aqg_i128 h = vc == VC_U ? i128_from_u64(hi) : i128_from_i64((int64_t)hi);
             aqg_i128 sh = {h.lo << 32, (h.hi << 32) | (h.lo >> 32)};
@@ -215,7 +217,7 @@ __device__ inline void emit_record_from(const R& rec, uint32_t g, const EmitSpec
         switch (a.op) {
         case AQG_RED_SUM: case AQG_RED_SUMSQ:                           // -> GetLongType
             if (vc == VC_F) put(a.out, g, __builtin_bit_cast(double, v0));
-            else put(a.out, g, sum128(a.acc0, a.acc1));
+            else put(a.out, g, sum128(a.acc0, a.acc1, a.op == AQG_RED_SUMSQ));
             break;
         case AQG_RED_COUNT: put(a.out, g, (uint64_t)cnt); break;
         case AQG_RED_AVG: {                                             // sum / (double)size
@@ -228,7 +230,7 @@ __device__ inline void emit_record_from(const R& rec, uint32_t g, const EmitSpec
                 double sd = __builtin_bit_cast(double, v0), q = __builtin_bit_cast(double, rec.acc(a.acc2));
                 d = (q - sd * sd / np1) / np1;
             } else {
-                aqg_i128 sm = sum128(a.acc0, a.acc1), q = sum128(a.acc2, a.acc3);
+                aqg_i128 sm = sum128(a.acc0, a.acc1), q = sum128(a.acc2, a.acc3, true);
                 aqg_i128 ss = i128_mul(sm, sm);                          // s * s in the 128-bit LongType (wraps like the reference)
                 d = (to_double(q) - to_double(ss) / np1) / np1;
             }

@@ -700,7 +700,8 @@ __global__ void __launch_bounds__(1024, 8) gid_agg_kernel(GidAgg a) {      // (e
                 if (vc == VC_F) { const double sd = __builtin_bit_cast(double, s), qd = __builtin_bit_cast(double, acc1[j]); d = (qd - sd * sd / np1) / np1; }
                 else {
                     const aqg_i128 sm = vc == VC_U ? i128_from_u64(s) : i128_from_i64((int64_t)s);
-                    const aqg_i128 qq = vc == VC_U ? i128_from_u64(acc1[j]) : i128_from_i64((int64_t)acc1[j]);
+                    // (uint16: the int squares wrap negative and the reference adds them sign-extended to its unsigned 128-bit sum)
+                    const aqg_i128 qq = vc == VC_U && a.vdt != AQG_UINT16 ? i128_from_u64(acc1[j]) : i128_from_i64((int64_t)acc1[j]);
                     const aqg_i128 ss = i128_mul(sm, sm);
                     const double sq = vc == VC_U ? u128_to_double(ss.hi, ss.lo) : i128_to_double(ss);
                     const double qdd = vc == VC_U ? u128_to_double(qq.hi, qq.lo) : i128_to_double(qq);

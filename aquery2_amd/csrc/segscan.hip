@@ -148,7 +148,11 @@ __global__ void __launch_bounds__(SB) seg_tile_scan_kernel(const T* __restrict__
             if constexpr (std::is_floating_point_v<T>) d = (run.q - run.s * run.s / np1) / np1;
             else {
                 const __int128 ss = (__int128)run.s * (__int128)run.s;                   // the reference's 128-bit LongType product (|s| < 2^63: no wrap)
-                d = ((double)run.q - i128_to_double(aqg_i128{(uint64_t)ss, (uint64_t)(ss >> 64)}) / np1) / np1;
+                // (uint16: the reference's sum of squares is an UNSIGNED 128-bit integer, and the int squares that wrapped negative are added
+                // to it sign-extended -- a negative 64-bit sum stands for 2^128 minus its magnitude; the rule of groupby_tail.hip's sum128)
+                double q;
+                if constexpr (std::is_same_v<T, uint16_t>) q = u128_to_double((uint64_t)(run.q >> 63), (uint64_t)run.q); else q = (double)run.q;
+                d = (q - i128_to_double(aqg_i128{(uint64_t)ss, (uint64_t)(ss >> 64)}) / np1) / np1;
             }
             o[j] = WR == SW_RED_STDDEV ? sqrt(d) : d;
         } else if constexpr (WR == SW_RAW) o[j] = run;

@@ -353,6 +353,9 @@ int aqg_grouped_ewise(aqg_ctx* ctx, aqg_groupby* g, int layout, int op, int kind
  * results are NOT bit-reproducible from run to run (the reference adds the rows of a group in one fixed order); every result lies
  * within (n_g - 1) 2^-53 sum|x| of the exactly rounded sum of its group (n_g rows), which is what the parity tests assert.
  * Integer aggregates, counts, MIN / MAX, keys, first rows and the group order are exact and deterministic.
+ * MIN / MAX of floating columns start from the reference's seeds, as in aqg_reduce: MAX from numeric_limits<T>::min() (a group of negative
+ * rows gives the smallest positive normal value), MIN from max() (a group whose rows are all +Inf gives the largest finite value); the same holds
+ * for aqg_grouped_reduce.  VAR / STDDEV of a uint16 column add the int squares sign-extended to the unsigned 128-bit sum, as the reference does.
  * On return the handle's ngroups is final; the device columns behind the handle (keys, first rows,
  * counts, results) may still be being written by kernels queued on the context's stream: read
  * them through this library (aqg_groupby_keys, aqg_d2h, ...: all ordered behind those kernels),

@@ -423,6 +423,17 @@ def sum_safe(x):
     return x
 
 
+def square_safe(x):
+    """full-exponent floating column scaled so that the squares, their sum AND the square of the sum (s * s <= n * ssq) stay finite in the
+    column's type: |x| <= sqrt(max / 2) / n"""
+    x = x.copy()
+    lim = np.sqrt(float(np.finfo(x.dtype).max) / 2) / max(len(x), 1)
+    big = np.abs(x) > lim
+    x[big] = (np.sign(x[big]) * np.ldexp(np.frexp(x[big])[0], int(np.floor(np.log2(lim))))).astype(x.dtype)
+    assert np.all(np.abs(x) <= lim)
+    return x
+
+
 def exact_sum(x):
     return sum(int(v) for v in x.tolist())
 

@@ -332,17 +332,6 @@ def test_reduce_floating(gpu, oracle, dt, n):
                     assert np.asarray(got).tobytes() == np.asarray(want).tobytes(), (cname, name, off, got, want)
 
 
-def square_safe(x):
-    """full-exponent floating column scaled so that the squares, their sum AND the square of the sum (s * s <= n * ssq) stay finite in the
-    column's type: |x| <= sqrt(max / 2) / n"""
-    x = x.copy()
-    lim = np.sqrt(float(np.finfo(x.dtype).max) / 2) / max(len(x), 1)
-    big = np.abs(x) > lim
-    x[big] = (np.sign(x[big]) * np.ldexp(np.frexp(x[big])[0], int(np.floor(np.log2(lim))))).astype(x.dtype)
-    assert np.all(np.abs(x) <= lim)
-    return x
-
-
 @pytest.mark.parametrize("dt", ex.FP_DTYPES, ids=ex.nm)
 @pytest.mark.parametrize("n", RED_N)
 def test_reduce_var_stddev_floating(gpu, oracle, dt, n):
@@ -351,7 +340,7 @@ def test_reduce_var_stddev_floating(gpu, oracle, dt, n):
     <= 2 n^2 2^-53 ssq (Cauchy-Schwarz), so |d var| <= 4 n 2^-52 ssq / (n + 1) with room for the three last roundings; stddev: that over
     sqrt(var).  Full range: the squares overflow on both sides -- the same infinity, or also a NaN."""
     fin = ex.one_sign_zeros(ex.unary_column(dt, n, 750 + n, nan=False, inf=False))
-    sq = square_safe(fin)
+    sq = ex.square_safe(fin)
     ssq = float(np.sum(sq.astype(np.float64) ** 2))
     bound = 4 * n * 2.0 ** -52 * ssq / (n + 1)
     for off in (0, 1):
