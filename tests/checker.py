@@ -155,6 +155,11 @@ class Checker:
         self._chk(self._f("scan")(op, t, _p(x), C.c_uint32(x.size), C.c_uint32(w), _p(out)), "scan")
         return out
 
+    def scan_at(self, op, t, x_addr, n, w, out_addr):
+        """scan of the n elements of dtype tag t at address x_addr into the buffer at out_addr: a slice of a larger column scanned in
+        place (the per-group compositions of tests/grouped_scan_cases.py make one such call for each of thousands of groups)"""
+        self._chk(self._f("scan")(op, t, C.c_void_p(x_addr), C.c_uint32(n), C.c_uint32(w), C.c_void_p(out_addr)), "scan")
+
     # -- gather / filter
     def gather(self, x, idx):
         x, idx = np.ascontiguousarray(x), np.ascontiguousarray(idx, dtype=np.uint32)
