@@ -36,6 +36,13 @@ MEDIAN_PROTOTYPES = {
     "aqg_grouped_median_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "aqg_select_last_routes": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
 }
+# ctypes prototypes of the top-k entries (applied by load_library)
+TOPK_MAX = 1024
+TOPK_PROTOTYPES = {
+    "aqg_topk": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
+    "aqg_grouped_topk": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "aqg_grouped_topk_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+}
 # ctypes prototypes of the count-distinct entries (applied by load_library)
 DISTINCT_PROTOTYPES = {
     "aqg_count_distinct": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)],
@@ -89,7 +96,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -627,6 +634,28 @@ class Device:
         r, p = C.c_uint32(), C.c_uint32()
         self._chk(self.lib.aqg_select_last_routes(self.ctx, C.byref(r), C.byref(p)), "aqg_select_last_routes")
         return r.value, p.value
+
+    # -- top-k (a selection built on the median's: include/aqg.h, top-k section)
+    def topk(self, x, k, order=ORDER_DESC, rows=False):
+        """the k largest (ORDER_DESC) or smallest (ORDER_ASC) elements of a column, in that order: k elements of the column's dtype,
+        zero past min(k, n); rows=True: also their row indices (np.uint32, 0xFFFFFFFF past min(k, n))"""
+        xd = self._dev(x)
+        vals = self.empty(max(int(k), 0), TAG2NP[xd.tag])
+        rid = self.empty(max(int(k), 0), np.uint32) if rows else None
+        self._chk(self.lib.aqg_topk(self.ctx, order, xd.tag, xd.ptr, xd.n, k, vals.ptr, rid.ptr if rows else None), "aqg_topk")
+        return (vals.to_host(), rid.to_host()) if rows else vals.to_host()
+
+    def grouped_topk(self, gb, x, k, order=ORDER_DESC, flat=False, pos=False):
+        """the top k of every group of a build, a (G, k) array: `x` in row layout, or (flat=True) already in the flat layout.
+        pos=True: also the (G, k) np.uint32 flat-layout positions of the elements (0xFFFFFFFF past a group's rows)"""
+        xd = self._dev(x)
+        G = gb.ngroups
+        vals = self.empty(G * max(int(k), 0), TAG2NP[xd.tag])
+        pd = self.empty(G * max(int(k), 0), np.uint32) if pos else None
+        fn = self.lib.aqg_grouped_topk_flat if flat else self.lib.aqg_grouped_topk
+        self._chk(fn(self.ctx, gb.h, order, xd.tag, xd.ptr, k, vals.ptr, pd.ptr if pos else None), "aqg_grouped_topk")
+        v = vals.to_host().reshape(G, int(k))
+        return (v, pd.to_host().reshape(G, int(k))) if pos else v
 
     # -- count distinct (include/aqg.h, count distinct section)
     def count_distinct(self, x):

@@ -235,6 +235,40 @@ int aqg_grouped_median(aqg_ctx* ctx, struct aqg_groupby* g, int which, int t, co
 int aqg_grouped_median_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, int t, const void* xflat, void* out_dev);
 int aqg_select_last_routes(aqg_ctx* ctx, uint32_t* routes_host, uint32_t* passes_host);
 
+/* ---- top-k -------------------------------------------------------------------
+ * The k largest or k smallest elements of a column, of every group: h2o Q8 (`-- select top 2 from each grp`,
+ * benchmark/h2o/groupby.sql:16-17, where the emitted `v3[val].subvec(0, 2)` returns the first two entries of the group's row list
+ * instead) and `ORDER BY x DESC LIMIT k` (engine/ast.py:451-454 sorts every row to print k).  A device SELECTION built on the median's
+ * radix selection: rows are never moved.
+ * Order: that of aqg_sort_rows.  AQG_ORDER_DESC: the k largest, largest first; AQG_ORDER_ASC: the k smallest, smallest first;
+ * AQG_ORDER_NEG: AQG_ERR_ARG.  Integers and BOOL by value.  Floating columns: -0.0 and +0.0 are one value; every NaN is one value
+ * above +inf, so NaNs come first under DESC.
+ * Output, for group g of c rows and m = min(k, c) (aqg_topk: "group 0" is the whole column, c = n, and rows_out takes the place of
+ * pos_out and holds row indices):
+ *   vals_out[g*k + j], j < m   the j-th row of the group in that order, AN ELEMENT OF THE INPUT bit for bit
+ *   pos_out[g*k + j],  j < m   that element's position (pos_out may be NULL).  Grouped calls: a position of the FLAT LAYOUT, in
+ *                              [offsets[g], offsets[g+1]); the row id is row_ids[pos] of aqg_groupby_postproc.  vals_out[g*k+j] is
+ *                              bitwise the column's element at pos_out[g*k+j]; the positions of a group are distinct, and among
+ *                              slots of equal image (equal values; the two zeros; the NaNs) they ascend.
+ *   slots j >= m               zero bytes in vals_out, 0xFFFFFFFF in pos_out (the missing-row marker of aqg_gather_fill)
+ * When more rows tie on the k-th image than there are slots left, which of them are taken is unspecified (it may differ between
+ * calls); the slots still hold distinct, ascending positions of rows with that image.
+ * 1 <= k <= AQG_TOPK_MAX, anything else AQG_ERR_ARG.  Dtypes: those of aqg_median (INT8/16/32/64, UINT8/16/32/64, BOOL, FLOAT,
+ * DOUBLE); anything else returns AQG_ERR_DTYPE with nothing written.
+ *   aqg_topk               the whole column; vals_out_dev: k elements, rows_out_dev: k uint32 or NULL.  n == 0: AQG_OK, k empty slots.
+ *   aqg_grouped_topk       G*k elements for all G groups in group order, x in ROW layout (brought into the flat layout in workspace)
+ *   aqg_grouped_topk_flat  the same over a column already in the FLAT LAYOUT of the build
+ * The grouped forms need a handle of aqg_groupby_build (a handle of aqg_groupby_agg: AQG_ERR_ARG, as the median); G == 0 or n == 0
+ * returns AQG_OK.  The input is never modified.  Asynchronous on the context's stream with no host round trip (aqg_topk too: the
+ * host knows min(k, n)), scratch from the context workspace, no allocation in steady state, and a number of launches that does not
+ * depend on the group count.  Routes and thresholds are the median's (AQG_SELECT_SMALL_MAX, AQG_SELECT_SPLIT_MIN; DESIGN.md section
+ * 4.11); aqg_select_last_routes reports, for these calls too, the mask of routes taken and the largest number of passes over its
+ * rows any group needed -- here the digit passes of the threshold search plus the one pass that collects (SMALL: 1).            */
+enum { AQG_TOPK_MAX = 1024 };
+int aqg_topk(aqg_ctx* ctx, int order, int t, const void* x, uint32_t n, uint32_t k, void* vals_out_dev, uint32_t* rows_out_dev);
+int aqg_grouped_topk(aqg_ctx* ctx, struct aqg_groupby* g, int order, int t, const void* x, uint32_t k, void* vals_out_dev, uint32_t* pos_out_dev);
+int aqg_grouped_topk_flat(aqg_ctx* ctx, struct aqg_groupby* g, int order, int t, const void* xflat, uint32_t k, void* vals_out_dev, uint32_t* pos_out_dev);
+
 /* ---- count distinct ----------------------------------------------------------
  * `count(distinct x)`: the generator emits `(x).distinct_size()` (common/types.py:271-277), under GROUP BY `(x[val]).distinct_size()`
  * inside the generated loop (engine/ast.py:749-784).  Replaces vector_type::distinct_size (server/vector_type.hpp:153-174) and

@@ -54,6 +54,37 @@ template <class T, template <typename...> class VT, class Ret> inline void devic
     if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
 }
 template <class T> using fp_of_long = types::GetFPType<types::GetLongType<T>>;   // double for every numeric T
+
+// ret[0, m) = the m = min(k, arr.size) largest (AQG_ORDER_DESC) / smallest (AQG_ORDER_ASC) elements of arr, in that order (include/aqg.h,
+// top-k section); `ret` holds at least m elements.  A per-group temporary of the generated loop that is all of its group is answered for
+// ALL groups by one grouped call (Runtime::deferred_topk) and copied on the host; any other vector goes through aqg_topk.  k above
+// AQG_TOPK_MAX, and the 128-bit element types, sort that vector's rows (aqg_sort_rows) and gather the first m.
+template <class T, template <typename...> class VT, class Ret> inline void device_topk(int order, uint32_t k, const VT<T>& arr, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    static_assert(std::is_same_v<RT, std::remove_cv_t<T>>, "maxk / mink: the result holds elements of the input");
+    auto& rt = dev::Runtime::get();
+    const uint32_t n = arr.size, m = n < k ? n : k;
+    if (m == 0) return;
+    constexpr bool selectable = sizeof(T) <= 8;
+    if (selectable && k <= AQG_TOPK_MAX && rt.deferred_topk(arr.container, n, order, k, ret.container)) {
+        rt.forget_range(ret.container, (size_t)m * sizeof(T));         // (host memory written here: no device result stands behind it)
+        return;
+    }
+    void* dout = rt.result(ret.container, (size_t)m * sizeof(T));
+    dev::In in(arr.container, (size_t)n * sizeof(T), arr.capacity == 0);
+    if (selectable && k <= AQG_TOPK_MAX) {
+        dev::check(aqg_topk(rt.ctx(), order, dev::tag_of<T>::value, in.d, n, m, dout, nullptr), "aqg_topk");
+    } else {
+        void* rows = nullptr;
+        dev::check(aqg_malloc(rt.ctx(), (size_t)n * 4, &rows), "aqg_malloc");
+        const int tag = dev::tag_of<T>::value;
+        const void* keys[1] = {in.d};
+        dev::check(aqg_sort_rows(rt.ctx(), 1, &tag, keys, &order, n, nullptr, n, static_cast<uint32_t*>(rows)), "aqg_sort_rows");
+        dev::check(aqg_gather(rt.ctx(), tag, in.d, static_cast<const uint32_t*>(rows), m, dout), "aqg_gather");
+        aqg_free(rt.ctx(), rows);
+    }
+    if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+}
 } // namespace aq
 
 // ---- reductions ---------------------------------------------------------------------------------------------------
@@ -97,6 +128,18 @@ T median(const VT<T>& v) {
     std::memcpy(&r, buf, sizeof(T));
     return r;
 }
+
+// maxk(k, v) / mink(k, v): the min(k, v.size) largest / smallest elements of v, largest / smallest first (h2o Q8 `largest two v3 by id6`;
+// the order of aqg_sort_rows: NaNs above +inf, the two zeros one value).  The reference's header has neither; they stand in the family of
+// maxw / minw (the count first).  The out-parameter form fills the first min(k, v.size) elements of `ret`.  Empty input: an empty vector.
+template <class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+void maxk(uint32_t k, const VT<T>& v, Ret& ret) { aq::device_topk(AQG_ORDER_DESC, k, v, ret); }
+template <class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+void mink(uint32_t k, const VT<T>& v, Ret& ret) { aq::device_topk(AQG_ORDER_ASC, k, v, ret); }
+template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+inline decayed_t<VT, T> maxk(uint32_t k, const VT<T>& v) { decayed_t<VT, T> ret(v.size < k ? v.size : k); aq::device_topk(AQG_ORDER_DESC, k, v, ret); return ret; }
+template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+inline decayed_t<VT, T> mink(uint32_t k, const VT<T>& v) { decayed_t<VT, T> ret(v.size < k ? v.size : k); aq::device_topk(AQG_ORDER_ASC, k, v, ret); return ret; }
 
 template <class T, template <typename...> class VT, class T2, template <typename...> class VT2,
           std::enable_if_t<aq::is_vt<VT, T> && aq::is_vt<VT2, T2>>* = nullptr>
@@ -184,7 +227,7 @@ template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constex
 AQ_SCALAR_ID(max) AQ_SCALAR_ID(min) AQ_SCALAR_ID(avg) AQ_SCALAR_ID(sum) AQ_SCALAR_ID(maxs) AQ_SCALAR_ID(mins) AQ_SCALAR_ID(avgs)
 AQ_SCALAR_ID(sums) AQ_SCALAR_ID(last) AQ_SCALAR_ID(first) AQ_SCALAR_ID(prev) AQ_SCALAR_ID(aggnext) AQ_SCALAR_ID(median)
 AQ_SCALAR_ZERO(var) AQ_SCALAR_ZERO(vars) AQ_SCALAR_ZERO(stddev) AQ_SCALAR_ZERO(stddevs) AQ_SCALAR_ZERO(deltas)
-AQ_SCALAR_WID(maxw) AQ_SCALAR_WID(minw) AQ_SCALAR_WID(avgw) AQ_SCALAR_WID(sumw)
+AQ_SCALAR_WID(maxw) AQ_SCALAR_WID(minw) AQ_SCALAR_WID(avgw) AQ_SCALAR_WID(sumw) AQ_SCALAR_WID(maxk) AQ_SCALAR_WID(mink)
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T varw(uint32_t, const T&) { return 0; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T stddevw(uint32_t, const T&) { return 0; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T ratiow(uint32_t, const T&) { return 1; }

@@ -69,6 +69,8 @@ struct GroupCtx {
     // (column, op) -> G result slots of 16 bytes, filled for ALL groups by one kernel on first request
     std::map<std::pair<int, int>, std::vector<unsigned char>> cache;
     std::map<std::pair<int, int>, std::vector<double>> corr_cache;
+    // (column, order, k) -> the G x k values of maxk / mink, filled for ALL groups by one aqg_grouped_topk on first request
+    std::map<std::array<uint32_t, 3>, std::vector<unsigned char>> topk_cache;
 };
 
 struct Entry {
@@ -324,7 +326,7 @@ public:
     }
     void free_vcols(GroupCtx* c) {
         for (auto& v : c->vcols) { if (v.dptr) aqg_free(ctx(), v.dptr); if (v.flat) aqg_free(ctx(), v.flat); }
-        c->vcols.clear(); c->memo.clear(); c->smemo.clear(); c->cache.clear(); c->corr_cache.clear();
+        c->vcols.clear(); c->memo.clear(); c->smemo.clear(); c->cache.clear(); c->corr_cache.clear(); c->topk_cache.clear();
     }
 
     // the deferred entry AT host address p (a per-group temporary), or nullptr
@@ -371,7 +373,7 @@ public:
     // DEFERRED_MEDIAN (`median(col[vecs[g]])`: aqg_grouped_median / aqg_grouped_median_flat, result in the column's own type)
     // DEFERRED_DISTINCT (`(col[vecs[g]]).distinct_size()`: aqg_grouped_count_distinct / _flat, a uint32 per group)
     static constexpr int DEFERRED_MEDIAN = 1000, DEFERRED_DISTINCT = 1001;
-    size_t grouped_calls = 0;      // aqg_grouped_reduce / _reduce_flat / _median / _median_flat / _count_distinct / _count_distinct_flat calls made so far (the tests count them)
+    size_t grouped_calls = 0;      // aqg_grouped_reduce / _reduce_flat / _median / _median_flat / _count_distinct / _count_distinct_flat / _topk / _topk_flat calls made so far (the tests count them)
     // the vector of `size` elements at p is a per-group temporary AND all of its group (a shorter view -- subvec shares the address -- is not)
     bool deferred_whole(const void* p, uint32_t size) {
         Entry* e = deferred_at(p);
@@ -414,6 +416,41 @@ public:
             hit = c->cache.emplace(key, std::move(slots)).first;
         }
         std::memcpy(out16, &hit->second[(size_t)e.dg * 16], 16);
+        return true;
+    }
+    // maxk / mink (order: AQG_ORDER_DESC / ASC, 1 <= k <= AQG_TOPK_MAX) of the per-group temporary of `size` elements at p, when it is all
+    // of its group (deferred_whole): ONE aqg_grouped_topk (a table column) or aqg_grouped_topk_flat (a virtual column) for all groups, the
+    // G x k values brought to the host once and cached under (column, order, k); out receives this group's min(k, size) elements
+    bool deferred_topk(const void* p, uint32_t size, int order, uint32_t k, void* out) {
+        if (!deferred_whole(p, size)) return false;
+        Entry& e = *deferred_at(p);
+        GroupCtx* c = e.dgroup;
+        const int tag = c->vcols[e.dv].tag;
+        const size_t es = esz(tag);
+        const std::array<uint32_t, 3> key{(uint32_t)e.dv, (uint32_t)order, k};
+        auto hit = c->topk_cache.find(key);
+        if (hit == c->topk_cache.end()) {
+            void* dout = nullptr;
+            int rc = aqg_malloc(ctx(), (size_t)c->G * k * es + 16, &dout);
+            if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+            ++grouped_calls;
+            if (c->vcols[e.dv].layout == 1) {
+                rc = aqg_grouped_topk_flat(ctx_, c->handle, order, tag, c->vcols[e.dv].dptr, k, dout, nullptr);
+                if (rc != AQG_OK) die("aqg_grouped_topk_flat", rc, ctx_);
+            } else {
+                void* tmp = nullptr;
+                const void* dsrc = vcol_row_ptr(c, e.dv, &tmp);
+                rc = aqg_grouped_topk(ctx_, c->handle, order, tag, dsrc, k, dout, nullptr);
+                if (rc != AQG_OK) die("aqg_grouped_topk", rc, ctx_);
+                release(tmp);
+            }
+            std::vector<unsigned char> vals((size_t)c->G * k * es);
+            rc = aqg_d2h(ctx_, vals.data(), dout, vals.size());
+            if (rc != AQG_OK) die("aqg_d2h", rc, ctx_);
+            aqg_free(ctx_, dout);
+            hit = c->topk_cache.emplace(key, std::move(vals)).first;
+        }
+        std::memcpy(out, &hit->second[(size_t)e.dg * k * es], (size_t)(size < k ? size : k) * es);
         return true;
     }
     // corr(<temporary>, <temporary>) of the same group, both row-order columns: aqg_grouped_corr once for all groups
