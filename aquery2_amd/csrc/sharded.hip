@@ -136,7 +136,13 @@ int aqg_reduce_sharded(aqg_comm* comm, int op, int t, const void* x, uint32_t n,
             if (!g.rows(r)) continue;
             const uint64_t* m = g.moments(r);
             if constexpr (FP) { double a, b; memcpy(&a, &m[0], 8); memcpy(&b, &m[2], 8); sd += a; qd += b; }
-            else { si = (__int128)((unsigned __int128)si + (unsigned __int128)i128_of(m)); qi = (__int128)((unsigned __int128)qi + (unsigned __int128)i128_of(m + 2)); }
+            else {
+                si = (__int128)((unsigned __int128)si + (unsigned __int128)i128_of(m));
+                // uint16: the wrapped `int` squares are exact in the shard's LOW word as a signed value and the reference adds them sign-extended
+                // (reduce.hip, aqg_reduce's epilogue): the high word of such a shard's sum of squares is not part of it
+                if constexpr (std::is_unsigned_v<T> && sizeof(T) == 2) qi = (__int128)((unsigned __int128)qi + (unsigned __int128)(__int128)(int64_t)m[2]);
+                else qi = (__int128)((unsigned __int128)qi + (unsigned __int128)i128_of(m + 2));
+            }
             const T a = from_word<T>(m[4]), b = from_word<T>(m[5]);
             mn = a < mn ? a : mn; mx = b > mx ? b : mx;
         }
@@ -212,16 +218,18 @@ int aqg_scan_sharded(aqg_comm* comm, int op, int t, const void* x, uint32_t n, u
     void* mom = nullptr;
     int lrc = AQG_OK;
     const int flags = prefix_sum ? 1 : (prefix_mm || running_mm) ? 4 : 0;
-    // the running max a window degrades to carries no numeric_limits seed, but the moments' max does (aggregations.h:73: for floating
-    // columns the smallest POSITIVE value): such a shard's true maximum is the last element of its own running max
-    const bool true_max = running_mm && op == AQG_SCAN_MAXW && dt_is_fp(t);
+    // the running min / max a window degrades to carries no numeric_limits seed, but the moments' min / max do (aggregations.h:73,81: for
+    // floating columns the smallest POSITIVE value, and the largest FINITE one -- below +Inf): such a shard's true extreme is the last
+    // element of its own running min / max
+    const bool true_ext = running_mm && dt_is_fp(t);
+    const size_t ext_off = op == AQG_SCAN_MAXW ? 40 : 32;
     if (flags && n) {
         lrc = aqg_malloc(ctx, 64, &mom);
         if (lrc == AQG_OK) lrc = aqg_stats_dev(ctx, t, x, n, flags, mom);
-        if (lrc == AQG_OK && true_max) {
+        if (lrc == AQG_OK && true_ext) {
             lrc = aqg_scan_minmax_seeded(ctx, op, t, x, n, nullptr, out);
-            if (lrc == AQG_OK) lrc = aqg_memset(ctx, static_cast<char*>(mom) + 40, 0, 8);
-            if (lrc == AQG_OK) lrc = aqg_d2d(ctx, static_cast<char*>(mom) + 40, static_cast<const char*>(out) + (size_t)(n - 1) * esz, esz);
+            if (lrc == AQG_OK) lrc = aqg_memset(ctx, static_cast<char*>(mom) + ext_off, 0, 8);
+            if (lrc == AQG_OK) lrc = aqg_d2d(ctx, static_cast<char*>(mom) + ext_off, static_cast<const char*>(out) + (size_t)(n - 1) * esz, esz);
         }
     }
     Gathered g;
@@ -268,7 +276,7 @@ int aqg_scan_sharded(aqg_comm* comm, int op, int t, const void* x, uint32_t n, u
             return AQG_OK;
         });
         AQG_TRY(rc);
-        if (true_max) return any ? aqg_scan_minmax_seeded(ctx, op, t, out, n, seed, out) : AQG_OK;      // (out is the shard's own running max already: max with the seed, in place)
+        if (true_ext) return any ? aqg_scan_minmax_seeded(ctx, op, t, out, n, seed, out) : AQG_OK;      // (out is the shard's own running min / max already: fold the seed in, in place)
         return aqg_scan_minmax_seeded(ctx, op, t, x, n, any ? seed : nullptr, out);
     }
     // ---- windows and shifts: the single-GPU kernel over the shard, then the rows that see the halo ------------------------------------
@@ -291,7 +299,10 @@ int aqg_scan_sharded(aqg_comm* comm, int op, int t, const void* x, uint32_t n, u
         return AQG_OK;
     }
     const uint32_t reach = window ? ww : 1u;                                   // rows of halo that matter / rows of the shard that see it
-    if (before == 0 || reach == 0) return AQG_OK;
+    // ratiow over the column's FIRST rows when they are no longer than the window but the column is: aqg_scan over the shard alone took the
+    // reference's short-column form (every row over its predecessor); the rows go through the padded column below, without a halo
+    const bool short_first = op == AQG_SCAN_RATIOW && before == 0 && total > ww && n <= ww;
+    if ((before == 0 && !short_first) || reach == 0) return AQG_OK;
     const uint32_t h = before < reach ? (uint32_t)before : reach;
     const uint32_t m = n < reach ? n : reach;
     // ratiow keeps its window only while the column is longer than it: pad the small column beyond w when the whole column is

@@ -246,6 +246,23 @@ def _fail(what, op, bad, got, want, extra=""):
     raise AssertionError(f"{what}: {RED_NAME[op]}: group {g} (of {int(bad.sum())} wrong): device {got[g]!r}, oracle {want[g]!r} {extra}")
 
 
+def fp_sum_bound(op, st, want):
+    """the bound of a floating SUM / AVG per group (module docstring): 2 n_g 2^-53 sum|x_g| (over n_g for AVG) plus one ulp of the result"""
+    ng = st["n"]
+    bound = 2 * ng * 2.0 ** -53 * st["sum_abs"]
+    if op == AVG:
+        bound = bound / ng
+    return bound + np.spacing(np.abs(np.where(np.isfinite(want), want, 0.0)))
+
+
+def fp_sum_ratio(op, got, want, st):
+    """largest |got - want| / fp_sum_bound over the groups compare() holds to that bound (no NaN row, a finite oracle value): what a test reports"""
+    with np.errstate(all="ignore"):
+        live = ~st["nan"] & np.isfinite(want) & np.isfinite(got)
+        r = np.abs(got - want)[live] / fp_sum_bound(op, st, want)[live]
+    return float(r.max()) if len(r) else 0.0
+
+
 def compare(op, x, got, want, o, what, stats=None):
     """one result column against the oracle's (module docstring); returns the share of the groups that were compared"""
     G = o["ngroups"]
@@ -265,10 +282,7 @@ def compare(op, x, got, want, o, what, stats=None):
             if bad.any():
                 _fail(what, op, bad, got, want)
         elif op in (SUM, AVG):
-            bound = 2 * ng * 2.0 ** -53 * st["sum_abs"]
-            if op == AVG:
-                bound = bound / ng
-            bound = bound + np.spacing(np.abs(np.where(np.isfinite(want), want, 0.0)))
+            bound = fp_sum_bound(op, st, want)
             fin, inf, nan = np.isfinite(want), np.isinf(want), np.isnan(want)
             bad = keep & ((fin & ~(np.abs(got - want) <= bound)) | (inf & (got != want)) | (nan & ~np.isnan(got)))
             if bad.any():

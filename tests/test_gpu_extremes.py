@@ -332,6 +332,33 @@ def test_reduce_floating(gpu, oracle, dt, n):
                     assert np.asarray(got).tobytes() == np.asarray(want).tobytes(), (cname, name, off, got, want)
 
 
+def var_bound(x):
+    """4 n 2^-52 ssq / (n + 1): the bound of test_reduce_var_stddev_floating's docstring for a column whose squares stay finite"""
+    n = len(x)
+    with np.errstate(over="ignore"):
+        return 4 * n * 2.0 ** -52 * float(np.sum(x.astype(np.float64) ** 2)) / (n + 1)
+
+
+def check_var_stddev_safe(gv, wv, gs, ws, bound, what=()):
+    """var and stddev of a square_safe column (device gv / gs, oracle wv / ws) under `bound` = var_bound of the column"""
+    gv, wv, gs, ws = float(gv), float(wv), float(gs), float(ws)
+    assert np.isfinite(wv) and abs(gv - wv) <= bound, ("var",) + tuple(what) + (gv, wv, bound)
+    if wv > bound:
+        assert abs(gs - ws) <= bound / np.sqrt(wv - bound) + 2.0 ** -52 * ws, ("stddev",) + tuple(what) + (gs, ws)
+    else:                                            # a variance within its own error of zero: either side may take the root of a negative number
+        assert np.isnan(gs) or abs(gs - (ws if np.isfinite(ws) else 0.0)) <= np.sqrt(2 * bound), ("stddev",) + tuple(what) + (gs, ws)
+
+
+def check_var_stddev_any(name, got, want, x, what=()):
+    """var / stddev of a column whose squares may overflow: inside var_bound where the oracle's value is finite, else the same infinity, or also a NaN"""
+    got, want = float(got), float(want)
+    if np.isfinite(want):                            # (short columns: nothing overflowed)
+        tol = var_bound(x)
+        assert abs(got - want) <= (tol if name == "var" else max(np.sqrt(tol), tol / max(want, 1e-300))), tuple(what) + (name, got, want)
+    else:
+        assert got == want if np.isinf(want) else np.isnan(got), tuple(what) + (name, got, want)
+
+
 @pytest.mark.parametrize("dt", ex.FP_DTYPES, ids=ex.nm)
 @pytest.mark.parametrize("n", RED_N)
 def test_reduce_var_stddev_floating(gpu, oracle, dt, n):
@@ -341,26 +368,14 @@ def test_reduce_var_stddev_floating(gpu, oracle, dt, n):
     sqrt(var).  Full range: the squares overflow on both sides -- the same infinity, or also a NaN."""
     fin = ex.one_sign_zeros(ex.unary_column(dt, n, 750 + n, nan=False, inf=False))
     sq = ex.square_safe(fin)
-    ssq = float(np.sum(sq.astype(np.float64) ** 2))
-    bound = 4 * n * 2.0 ** -52 * ssq / (n + 1)
+    bound = var_bound(sq)
     for off in (0, 1):
         d = view(gpu, sq, off)
-        gv, wv = float(gpu.reduce(ck.RED_VAR, d)), float(oracle.reduce(ck.RED_VAR, sq))
-        assert np.isfinite(wv) and abs(gv - wv) <= bound, ("var", off, gv, wv, bound)
-        gs, ws = float(gpu.reduce(ck.RED_STDDEV, d)), float(oracle.reduce(ck.RED_STDDEV, sq))
-        if wv > bound:
-            assert abs(gs - ws) <= bound / np.sqrt(wv - bound) + 2.0 ** -52 * ws, ("stddev", off, gs, ws)
-        else:                                            # a variance within its own error of zero: either side may take the root of a negative number
-            assert np.isnan(gs) or abs(gs - (ws if np.isfinite(ws) else 0.0)) <= np.sqrt(2 * bound), ("stddev", off, gs, ws)
+        check_var_stddev_safe(gpu.reduce(ck.RED_VAR, d), oracle.reduce(ck.RED_VAR, sq), gpu.reduce(ck.RED_STDDEV, d), oracle.reduce(ck.RED_STDDEV, sq), bound, (off,))
         for cname, x in (("full range", fin),) + fp_columns(dt, n, 760 + n):
             dx = view(gpu, x, off)
             for name in ("var", "stddev"):
-                got, want = float(gpu.reduce(ck.RED_NAMES[name], dx)), float(oracle.reduce(ck.RED_NAMES[name], x))
-                if np.isfinite(want):                    # (short columns: nothing overflowed)
-                    tol = 4 * n * 2.0 ** -52 * float(np.sum(x.astype(np.float64) ** 2)) / (n + 1)
-                    assert abs(got - want) <= (tol if name == "var" else max(np.sqrt(tol), tol / max(want, 1e-300))), (cname, name, off, got, want)
-                else:
-                    assert got == want if np.isinf(want) else np.isnan(got), (cname, name, off, got, want)
+                check_var_stddev_any(name, gpu.reduce(ck.RED_NAMES[name], dx), oracle.reduce(ck.RED_NAMES[name], x), x, (cname, off))
 
 
 @pytest.mark.parametrize("dt", ex.FP_DTYPES, ids=ex.nm)
@@ -509,15 +524,23 @@ def check_fp_sums(name, got, want, x, w=None, route=None):
         r = int(np.nonzero(bad)[0][0])
         raise AssertionError(f"{name} w={w}: row {r}: device {g[r]!r}, oracle {t[r]!r}, bound {b[r]!r}")
     if name in ("sumw", "avgw") and route in ("direct", "lds"):
-        ref, rb = window_reference(x, w, route)
-        if name == "avgw":
-            ln = np.minimum(i + 1, w)
-            ref, rb = ref / ln, rb / ln
-        with np.errstate(invalid="ignore"):
-            bad = np.isfinite(ref[:stop]) & np.isfinite(rb[:stop]) & ~(np.abs(g - ref[:stop]) <= rb[:stop])
-        if bad.any():
-            r = int(np.nonzero(bad)[0][0])
-            raise AssertionError(f"{name} w={w} ({route} route): row {r}: device {g[r]!r}, sum of the route's rows {ref[r]!r}, bound {rb[r]!r}")
+        check_window_route(name, g, x, w, route)
+
+
+def check_window_route(name, g, x, w, route, first=0):
+    """floating sumw / avgw rows `first` ... len(g) - 1 of `g` (double; the caller has cut it at the oracle's first NaN output) against window_reference:
+    the sum of the rows the direct / lds route adds over the column `x`, under the bound over those rows"""
+    stop = len(g)
+    ref, rb = window_reference(x, w, route)
+    if name == "avgw":
+        ln = np.minimum(np.arange(len(x), dtype=np.float64) + 1, w)
+        ref, rb = ref / ln, rb / ln
+    with np.errstate(invalid="ignore"):
+        bad = np.isfinite(ref[:stop]) & np.isfinite(rb[:stop]) & ~(np.abs(g - ref[:stop]) <= rb[:stop])
+    bad[:first] = False
+    if bad.any():
+        r = int(np.nonzero(bad)[0][0])
+        raise AssertionError(f"{name} w={w} ({route} route): row {r}: device {g[r]!r}, sum of the route's rows {ref[r]!r}, bound {rb[r]!r}")
 
 
 def check_int_avgw(got, x, w):
