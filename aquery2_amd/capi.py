@@ -43,6 +43,13 @@ TOPK_PROTOTYPES = {
     "aqg_grouped_topk": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
     "aqg_grouped_topk_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
 }
+# ctypes prototypes of the quantile entries (applied by load_library)
+QUANTILES_MAX = 8
+QUANTILE_PROTOTYPES = {
+    "aqg_quantiles": [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_grouped_quantiles": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_grouped_quantiles_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
+}
 # ctypes prototypes of the count-distinct entries (applied by load_library)
 DISTINCT_PROTOTYPES = {
     "aqg_count_distinct": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)],
@@ -96,7 +103,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -656,6 +663,28 @@ class Device:
         self._chk(fn(self.ctx, gb.h, order, xd.tag, xd.ptr, k, vals.ptr, pd.ptr if pos else None), "aqg_grouped_topk")
         v = vals.to_host().reshape(G, int(k))
         return (v, pd.to_host().reshape(G, int(k))) if pos else v
+
+    # -- quantiles (several ranks in one selection: include/aqg.h, quantiles section)
+    def quantiles(self, x, nums, den, which=SEL_LOWER):
+        """the rows of rank floor (SEL_LOWER) / ceil (SEL_UPPER) of nums[j] * (n - 1) / den of a column in ascending order, len(nums)
+        elements of the column's own dtype in the order of `nums` (zeros for an empty column)"""
+        xd = self._dev(x)
+        nq = len(nums)
+        na = (C.c_uint32 * max(1, nq))(*nums)
+        out = np.zeros(max(1, nq), TAG2NP[xd.tag])
+        self._chk(self.lib.aqg_quantiles(self.ctx, which, nq, na, den, xd.tag, xd.ptr, xd.n, out.ctypes.data), "aqg_quantiles")
+        return out[:nq]
+
+    def grouped_quantiles(self, gb, x, nums, den, which=SEL_LOWER, flat=False, keep=False, out=None):
+        """the quantiles nums[j] / den of every group of a build, a (G, len(nums)) array: `x` in row layout, or (flat=True) already
+        in the flat layout"""
+        xd = self._dev(x)
+        nq, G = len(nums), gb.ngroups
+        na = (C.c_uint32 * max(1, nq))(*nums)
+        out = out if out is not None else self.empty(G * nq, TAG2NP[xd.tag])
+        fn = self.lib.aqg_grouped_quantiles_flat if flat else self.lib.aqg_grouped_quantiles
+        self._chk(fn(self.ctx, gb.h, which, nq, na, den, xd.tag, xd.ptr, out.ptr), "aqg_grouped_quantiles")
+        return out if keep else out.to_host().reshape(G, nq)
 
     # -- count distinct (include/aqg.h, count distinct section)
     def count_distinct(self, x):

@@ -269,6 +269,38 @@ int aqg_topk(aqg_ctx* ctx, int order, int t, const void* x, uint32_t n, uint32_t
 int aqg_grouped_topk(aqg_ctx* ctx, struct aqg_groupby* g, int order, int t, const void* x, uint32_t k, void* vals_out_dev, uint32_t* pos_out_dev);
 int aqg_grouped_topk_flat(aqg_ctx* ctx, struct aqg_groupby* g, int order, int t, const void* xflat, uint32_t k, void* vals_out_dev, uint32_t* pos_out_dev);
 
+/* ---- quantiles ---------------------------------------------------------------
+ * Several ranks of a column, of every group, in ONE selection: `p95 / p99 of price by symbol`, the quartiles, or min, median and
+ * max in one go.  The median's radix selection with up to AQG_QUANTILES_MAX states per group: every pass over a group's rows serves
+ * all of its ranks, so nq ranks cost the passes of one.
+ * Rank: quantile j of a slice of c >= 1 rows is the row of rank r_j in ascending order -- the order of aqg_sort_rows under
+ * AQG_ORDER_ASC and of aqg_median (-0.0 and +0.0 one value, every NaN one value above +inf) -- with
+ *   r_j = floor(num[j] * (c - 1) / den)   AQG_SEL_LOWER
+ *   r_j = ceil (num[j] * (c - 1) / den)   AQG_SEL_UPPER
+ * exact (unsigned 64-bit arithmetic on the device, per group; nothing comes back to the host).  num[j] == 0 is the least row,
+ * num[j] == den the greatest, num = 1, den = 2 is aqg_median exactly for both values of `which`.  num may come in any order and may
+ * repeat; out[g * nq + j] answers num[j].  1 <= nq <= AQG_QUANTILES_MAX, den >= 1 and num[j] <= den, anything else AQG_ERR_ARG
+ * with nothing written.  num_host is read during the call and may be freed on return.
+ * Result: AN ELEMENT OF THE INPUT bit for bit, in the column's own dtype `t`, with the median's two caveats and no others: when the
+ * rank lands on a zero of a slice that holds both zeros, which zero comes back is unspecified; when it lands among the NaNs, some
+ * NaN comes back.  Interpolating quantiles (numpy's `linear`) stay with the caller: lower, upper and aqg_ewise, as for h2o's
+ * averaged median.
+ * Dtypes: those of aqg_median (INT8/16/32/64, UINT8/16/32/64, BOOL, FLOAT, DOUBLE); anything else (the 128-bit integers too) returns
+ * AQG_ERR_DTYPE with nothing written.
+ *   aqg_quantiles               the whole column; nq elements of dtype t in HOST memory.  n == 0: AQG_OK and nq zeroed elements.
+ *   aqg_grouped_quantiles       out_dev[g * nq + j] for all G groups in group order, x in ROW layout (brought into the flat layout in
+ *                               workspace, once whatever nq is)
+ *   aqg_grouped_quantiles_flat  the same over a column already in the FLAT LAYOUT of the build
+ * The grouped forms need a handle of aqg_groupby_build (a handle of aqg_groupby_agg: AQG_ERR_ARG, as the median); G == 0 returns
+ * AQG_OK.  The input is never modified.  Asynchronous on the context's stream (aqg_quantiles synchronises once for its host result),
+ * scratch from the context workspace, no allocation in steady state, and a number of launches that depends on the dtype's width
+ * only -- not on G and not on nq.  Routes and thresholds are the median's.  aqg_select_last_routes reports for these calls too: the
+ * route mask, and the largest number of passes over its rows any group needed -- a pass that serves several ranks counts once.   */
+enum { AQG_QUANTILES_MAX = 8 };
+int aqg_quantiles(aqg_ctx* ctx, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* x, uint32_t n, void* out_host);
+int aqg_grouped_quantiles(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* x, void* out_dev);
+int aqg_grouped_quantiles_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* xflat, void* out_dev);
+
 /* ---- count distinct ----------------------------------------------------------
  * `count(distinct x)`: the generator emits `(x).distinct_size()` (common/types.py:271-277), under GROUP BY `(x[val]).distinct_size()`
  * inside the generated loop (engine/ast.py:749-784).  Replaces vector_type::distinct_size (server/vector_type.hpp:153-174) and

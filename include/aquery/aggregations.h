@@ -5,6 +5,7 @@
 // at the bottom exactly like the reference's.
 #pragma once
 #include <cmath>
+#include <initializer_list>
 #include <limits>
 #include <utility>
 
@@ -85,6 +86,20 @@ template <class T, template <typename...> class VT, class Ret> inline void devic
     }
     if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
 }
+// out[0, nq) = the rows of rank floor (AQG_SEL_LOWER) / ceil (AQG_SEL_UPPER) of nums[j] (arr.size - 1) / den of arr in ascending order
+// (include/aqg.h, quantiles section), in the order of `nums`; `out` is host memory.  A per-group temporary of the generated loop that is
+// all of its group is answered for ALL groups by one grouped call (Runtime::deferred_quantiles); any other vector goes through
+// aqg_quantiles.  A list longer than AQG_QUANTILES_MAX is asked for in runs of that many.  Empty input: zeros.
+template <class T, template <typename...> class VT> inline void device_quantiles(int which, uint32_t den, const uint32_t* nums, uint32_t nq, const VT<T>& arr, T* out) {
+    auto& rt = dev::Runtime::get();
+    if (!arr.size) { for (uint32_t j = 0; j < nq; ++j) out[j] = T(0); return; }
+    for (uint32_t b = 0; b < nq; b += AQG_QUANTILES_MAX) {
+        const uint32_t m = nq - b < (uint32_t)AQG_QUANTILES_MAX ? nq - b : (uint32_t)AQG_QUANTILES_MAX;
+        if (rt.deferred_quantiles(arr.container, arr.size, which, den, nums + b, m, out + b)) continue;
+        dev::In in(arr.container, (size_t)arr.size * sizeof(T), arr.capacity == 0);     // not a deferred `col[vecs[g]]`: this very vector
+        dev::check(aqg_quantiles(rt.ctx(), which, m, nums + b, den, dev::tag_of<T>::value, in.d, arr.size, out + b), "aqg_quantiles");
+    }
+}
 } // namespace aq
 
 // ---- reductions ---------------------------------------------------------------------------------------------------
@@ -140,6 +155,30 @@ template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<V
 inline decayed_t<VT, T> maxk(uint32_t k, const VT<T>& v) { decayed_t<VT, T> ret(v.size < k ? v.size : k); aq::device_topk(AQG_ORDER_DESC, k, v, ret); return ret; }
 template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
 inline decayed_t<VT, T> mink(uint32_t k, const VT<T>& v) { decayed_t<VT, T> ret(v.size < k ? v.size : k); aq::device_topk(AQG_ORDER_ASC, k, v, ret); return ret; }
+
+// quantile(num, den, v): the row of rank floor(num (v.size - 1) / den) of v in ascending order -- the LOWER rank, an element of the input
+// (include/aqg.h, quantiles section); quantile(1, 2, v) is median(v).  Empty input: T(0), like median.
+// quantiles(den, {num...}, v): one element per num, in the order given, from ONE selection (p5 / p50 / p95 in the passes of one); the
+// out-parameter form fills the first nums.size() elements of `ret`.  Interpolated quantiles stay with the caller.
+template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+T quantile(uint32_t num, uint32_t den, const VT<T>& v) {
+    std::remove_cv_t<T> r;
+    aq::device_quantiles(AQG_SEL_LOWER, den, &num, 1, v, &r);
+    return r;
+}
+template <class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+void quantiles(uint32_t den, std::initializer_list<uint32_t> nums, const VT<T>& v, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    static_assert(std::is_same_v<RT, std::remove_cv_t<T>>, "quantiles: the result holds elements of the input");
+    aq::dev::Runtime::get().forget_range(ret.container, nums.size() * sizeof(T));      // (host memory written here: no device result stands behind it)
+    aq::device_quantiles(AQG_SEL_LOWER, den, nums.begin(), (uint32_t)nums.size(), v, ret.container);
+}
+template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+inline decayed_t<VT, T> quantiles(uint32_t den, std::initializer_list<uint32_t> nums, const VT<T>& v) {
+    decayed_t<VT, T> ret((uint32_t)nums.size());
+    quantiles(den, nums, v, ret);
+    return ret;
+}
 
 template <class T, template <typename...> class VT, class T2, template <typename...> class VT2,
           std::enable_if_t<aq::is_vt<VT, T> && aq::is_vt<VT2, T2>>* = nullptr>
@@ -232,6 +271,7 @@ template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constex
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T stddevw(uint32_t, const T&) { return 0; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T ratiow(uint32_t, const T&) { return 1; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T ratios(const T&) { return 1; }
+template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T quantile(uint32_t, uint32_t, const T& v) { return v; }
 #undef AQ_SCALAR_ID
 #undef AQ_SCALAR_ZERO
 #undef AQ_SCALAR_WID

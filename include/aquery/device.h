@@ -71,6 +71,8 @@ struct GroupCtx {
     std::map<std::pair<int, int>, std::vector<double>> corr_cache;
     // (column, order, k) -> the G x k values of maxk / mink, filled for ALL groups by one aqg_grouped_topk on first request
     std::map<std::array<uint32_t, 3>, std::vector<unsigned char>> topk_cache;
+    // (column, which, den, the num list) -> the G x nq values of quantile / quantiles, filled for ALL groups by one aqg_grouped_quantiles
+    std::map<std::vector<uint32_t>, std::vector<unsigned char>> quant_cache;
 };
 
 struct Entry {
@@ -326,7 +328,7 @@ public:
     }
     void free_vcols(GroupCtx* c) {
         for (auto& v : c->vcols) { if (v.dptr) aqg_free(ctx(), v.dptr); if (v.flat) aqg_free(ctx(), v.flat); }
-        c->vcols.clear(); c->memo.clear(); c->smemo.clear(); c->cache.clear(); c->corr_cache.clear(); c->topk_cache.clear();
+        c->vcols.clear(); c->memo.clear(); c->smemo.clear(); c->cache.clear(); c->corr_cache.clear(); c->topk_cache.clear(); c->quant_cache.clear();
     }
 
     // the deferred entry AT host address p (a per-group temporary), or nullptr
@@ -373,7 +375,7 @@ public:
     // DEFERRED_MEDIAN (`median(col[vecs[g]])`: aqg_grouped_median / aqg_grouped_median_flat, result in the column's own type)
     // DEFERRED_DISTINCT (`(col[vecs[g]]).distinct_size()`: aqg_grouped_count_distinct / _flat, a uint32 per group)
     static constexpr int DEFERRED_MEDIAN = 1000, DEFERRED_DISTINCT = 1001;
-    size_t grouped_calls = 0;      // aqg_grouped_reduce / _reduce_flat / _median / _median_flat / _count_distinct / _count_distinct_flat / _topk / _topk_flat calls made so far (the tests count them)
+    size_t grouped_calls = 0;      // aqg_grouped_reduce / _reduce_flat / _median / _median_flat / _count_distinct / _count_distinct_flat / _topk / _topk_flat / _quantiles / _quantiles_flat calls made so far (the tests count them)
     // the vector of `size` elements at p is a per-group temporary AND all of its group (a shorter view -- subvec shares the address -- is not)
     bool deferred_whole(const void* p, uint32_t size) {
         Entry* e = deferred_at(p);
@@ -451,6 +453,43 @@ public:
             hit = c->topk_cache.emplace(key, std::move(vals)).first;
         }
         std::memcpy(out, &hit->second[(size_t)e.dg * k * es], (size_t)(size < k ? size : k) * es);
+        return true;
+    }
+    // quantile / quantiles (which: AQG_SEL_LOWER / UPPER, 1 <= nq <= AQG_QUANTILES_MAX ranks num[j] / den) of the per-group temporary of
+    // `size` elements at p, when it is all of its group (deferred_whole): ONE aqg_grouped_quantiles (a table column) or
+    // aqg_grouped_quantiles_flat (a virtual column) for all groups, the G x nq values brought to the host once and cached under
+    // (column, which, den, the num list); out receives this group's nq elements
+    bool deferred_quantiles(const void* p, uint32_t size, int which, uint32_t den, const uint32_t* num, uint32_t nq, void* out) {
+        if (!deferred_whole(p, size)) return false;
+        Entry& e = *deferred_at(p);
+        GroupCtx* c = e.dgroup;
+        const int tag = c->vcols[e.dv].tag;
+        const size_t es = esz(tag);
+        std::vector<uint32_t> key{(uint32_t)e.dv, (uint32_t)which, den};
+        key.insert(key.end(), num, num + nq);
+        auto hit = c->quant_cache.find(key);
+        if (hit == c->quant_cache.end()) {
+            void* dout = nullptr;
+            int rc = aqg_malloc(ctx(), (size_t)c->G * nq * es + 16, &dout);
+            if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+            ++grouped_calls;
+            if (c->vcols[e.dv].layout == 1) {
+                rc = aqg_grouped_quantiles_flat(ctx_, c->handle, which, nq, num, den, tag, c->vcols[e.dv].dptr, dout);
+                if (rc != AQG_OK) die("aqg_grouped_quantiles_flat", rc, ctx_);
+            } else {
+                void* tmp = nullptr;
+                const void* dsrc = vcol_row_ptr(c, e.dv, &tmp);
+                rc = aqg_grouped_quantiles(ctx_, c->handle, which, nq, num, den, tag, dsrc, dout);
+                if (rc != AQG_OK) die("aqg_grouped_quantiles", rc, ctx_);
+                release(tmp);
+            }
+            std::vector<unsigned char> vals((size_t)c->G * nq * es);
+            rc = aqg_d2h(ctx_, vals.data(), dout, vals.size());
+            if (rc != AQG_OK) die("aqg_d2h", rc, ctx_);
+            aqg_free(ctx_, dout);
+            hit = c->quant_cache.emplace(std::move(key), std::move(vals)).first;
+        }
+        std::memcpy(out, &hit->second[(size_t)e.dg * nq * es], (size_t)nq * es);
         return true;
     }
     // corr(<temporary>, <temporary>) of the same group, both row-order columns: aqg_grouped_corr once for all groups
