@@ -69,6 +69,10 @@ JOIN_KEYS_PROTOTYPES = {
     "aqg_join_tuple_slots": [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "aqg_gather_fill": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
 }
+STR_ROUTE_HOST, STR_ROUTE_DEVICE, STR_ROUTE_FALLBACK = 1, 2, 4                          # aqg_str_encode_last
+STR_PROTOTYPES = {
+    "aqg_str_encode_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 PLAN_FAST_LDS, PLAN_SMALL_LDS, PLAN_BIG_LDS, PLAN_DENSE, PLAN_PART_ONE, PLAN_PART_TWO, PLAN_PART_ROUND1, PLAN_PART_WIDE, PLAN_SORTED_TAIL, PLAN_HBM_TABLE, PLAN_BUILD_PARTITIONED, PLAN_GID_PARTITION, PLAN_PACKED_VALUES, PLAN_RANGE_PARTITIONS, PLAN_ROW_EMIT, PLAN_PACKED_KEYS, PLAN_BUILD_LOOKUP = (1 << i for i in range(17))
 
 
@@ -103,7 +107,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -473,6 +477,12 @@ class Device:
         buf = DevBuf(self, raw.ptr, np.uint8, a.shape[0], owned=False)
         buf._raw, buf._tag = raw, tag
         return buf
+
+    def str_encode_last(self):
+        """(STR_ROUTE_* of the last aqg_str_encode on this device, 1 if its verify kernel saw a mismatch else 0)"""
+        r, m = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_str_encode_last(self.ctx, C.byref(r), C.byref(m)), "aqg_str_encode_last")
+        return r.value, m.value
 
     # -- generators
     def col_pin(self, a):

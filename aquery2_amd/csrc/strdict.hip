@@ -77,6 +77,13 @@ extern "C" int aqg_str_encode(aqg_ctx* ctx, const char* const* strs_host, uint32
     return str_encode_impl(ctx, strs_host, n, codes_dev, ndistinct_host, nullptr);
 }
 
+extern "C" int aqg_str_encode_last(aqg_ctx* ctx, uint32_t* route, uint32_t* mismatch) {
+    if (!ctx || !route || !mismatch) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_str_encode_last: bad argument");
+    *route = ctx->str_route;
+    *mismatch = ctx->str_mismatch;
+    return AQG_OK;
+}
+
 // astring_view keys of a table sharded by ROW RANGE: codes of ONE dictionary over all shards, in GLOBAL first-occurrence order (shards
 // are contiguous row ranges in rank order, so walking the ranks' dictionaries in rank order, each in its own first-occurrence order, is
 // the global first occurrence) -- the uint32 key column aqg_groupby_agg_sharded takes.  Every rank encodes its rows (aqg_str_encode), the
@@ -84,6 +91,7 @@ extern "C" int aqg_str_encode(aqg_ctx* ctx, const char* const* strs_host, uint32
 // the host and remap their code columns on the device.
 extern "C" int aqg_str_encode_sharded(aqg_comm* comm, const char* const* strs_host, uint32_t n, uint32_t* codes_dev, uint32_t* ndistinct_global_host) {
     aqg_ctx* ctx = aqg_comm_ctx(comm);
+    if (ctx) ctx->str_route = ctx->str_mismatch = 0;
     if (!comm || (!strs_host && n) || (!codes_dev && n)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_str_encode_sharded: bad argument");
     const int world = aqg_comm_world(comm), rank = aqg_comm_rank(comm);
     std::vector<uint32_t> first;
@@ -140,9 +148,14 @@ extern "C" int aqg_str_encode_sharded(aqg_comm* comm, const char* const* strs_ho
 
 namespace {
 int str_encode_impl(aqg_ctx* ctx, const char* const* strs_host, uint32_t n, uint32_t* codes_dev, uint32_t* ndistinct_host, std::vector<uint32_t>* first_rows) {
+    if (ctx) ctx->str_route = ctx->str_mismatch = 0;
     if (!ctx || (!strs_host && n) || (!codes_dev && n)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_str_encode: bad argument");
     constexpr uint32_t DEVICE_MIN = 1u << 16;                                  // rows from which the device builds the dictionary
-    if (aqg_switches().str_host || n < DEVICE_MIN) return encode_on_host(ctx, strs_host, n, codes_dev, ndistinct_host, first_rows);
+    if (aqg_switches().str_host || n < DEVICE_MIN) {
+        AQG_TRY(encode_on_host(ctx, strs_host, n, codes_dev, ndistinct_host, first_rows));
+        ctx->str_route = AQG_STR_ROUTE_HOST;
+        return AQG_OK;
+    }
     // ---- host: one walk over the strings, in parallel: lengths, offsets, bytes ---------------------------------------------------
     unsigned nt = std::thread::hardware_concurrency();
     nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
@@ -213,8 +226,14 @@ int str_encode_impl(aqg_ctx* ctx, const char* const* strs_host, uint32_t n, uint
     if (g) aqg_groupby_destroy(g);
     for (void* p : {dbytes, doff, dh, dlen, dmis}) if (p) aqg_free(ctx, p);
     if (rc != AQG_OK) return rc;
-    if (mism) return encode_on_host(ctx, strs_host, n, codes_dev, ndistinct_host, first_rows);      // different strings under one 64-bit hash and length
+    if (mism) {                                                                                      // different strings under one 64-bit hash and length
+        AQG_TRY(encode_on_host(ctx, strs_host, n, codes_dev, ndistinct_host, first_rows));
+        ctx->str_route = AQG_STR_ROUTE_FALLBACK;
+        ctx->str_mismatch = 1;
+        return AQG_OK;
+    }
     if (ndistinct_host) *ndistinct_host = G;
+    ctx->str_route = AQG_STR_ROUTE_DEVICE;
     return AQG_OK;
 }
 } // namespace

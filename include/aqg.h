@@ -366,6 +366,14 @@ int aqg_str_encode(aqg_ctx* ctx, const char* const* strs_host, uint32_t n, uint3
  * (two small collectives), merge them in rank order and remap their code columns on the device                                        */
 struct aqg_comm;
 int aqg_str_encode_sharded(struct aqg_comm* comm, const char* const* strs_host, uint32_t n, uint32_t* codes_dev, uint32_t* ndistinct_global_host);
+/* diagnostic of the last aqg_str_encode on this context (like aqg_join_last; the tests pin every route with it, the product does not
+ * look at it): the route -- HOST: the host map (fewer than 2^16 rows, or AQG_STR_HOST); DEVICE: the device dictionary was accepted;
+ * FALLBACK: the device dictionary was built, a row differed from its group's first row (two strings of one length under one 64-bit
+ * hash) and the call was redone by the host map -- and *mismatch = 1 when the verify kernel saw such a row, else 0.  The local
+ * encode inside aqg_str_encode_sharded is the last aqg_str_encode of that rank's context.  Both zero before any call, after an
+ * argument error and after a call that failed.                                                                                      */
+enum { AQG_STR_ROUTE_HOST = 1, AQG_STR_ROUTE_DEVICE = 2, AQG_STR_ROUTE_FALLBACK = 4 };
+int aqg_str_encode_last(aqg_ctx* ctx, uint32_t* route, uint32_t* mismatch);
 
 /* one aggregate over all groups in ONE pass over the value column: the device
  * form of the generated per-group loop `out[g] = op(col[vecs[g]])`
