@@ -69,6 +69,15 @@ JOIN_KEYS_PROTOTYPES = {
     "aqg_join_tuple_slots": [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "aqg_gather_fill": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
 }
+# ctypes prototypes of the as-of join (applied by load_library)
+ASOF_BACKWARD, ASOF_FORWARD = 0, 1
+ASOF_STRICT = 1                                                                        # flags
+ASOF_ROUTE_LDS, ASOF_ROUTE_HBM, ASOF_ROUTE_NOKEYS, ASOF_ROUTE_PRESORTED = 1, 2, 4, 8    # aqg_join_asof_last
+ASOF_PROTOTYPES = {
+    "aqg_join_asof": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                      C.c_int, C.c_void_p],
+    "aqg_join_asof_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 STR_ROUTE_HOST, STR_ROUTE_DEVICE, STR_ROUTE_FALLBACK = 1, 2, 4                          # aqg_str_encode_last
 STR_PROTOTYPES = {
     "aqg_str_encode_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -107,7 +116,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -914,6 +923,24 @@ class Device:
 
     def join_tuple_slots(self, cols, table_slots):
         return join_tuple_slots(cols, table_slots)
+
+    # -- as-of join (include/aqg.h): a side is a list of 0..8 key columns, as for join_keys_*, and its `on` column
+    def join_asof(self, build_cols, build_on, probe_cols, probe_on, direction=ASOF_BACKWARD, strict=False):
+        """np.uint32[np]: for every probe row the build row of its key tuple with the nearest `on` at or before (ASOF_BACKWARD) or at
+        or after (ASOF_FORWARD) its own -- strictly before / after under `strict` -- else 0xFFFFFFFF (aqg_join_asof)"""
+        bo, po = self._dev(build_on), self._dev(probe_on)
+        bd, dts, bp = self._keyargs(build_cols) if len(build_cols) else ([], None, None)
+        pd, _, pp = self._keyargs(probe_cols) if len(probe_cols) else ([], None, None)
+        out = self.empty(po.n, np.uint32)
+        self._chk(self.lib.aqg_join_asof(self.ctx, direction, ASOF_STRICT if strict else 0, len(bd), dts, bp, bo.ptr, bo.n, pp, po.ptr, po.n, bo.tag,
+                                         out.ptr), "aqg_join_asof")
+        return out.to_host()
+
+    def join_asof_last(self):
+        """(ASOF_ROUTE_* mask, distinct build tuples, digit passes of the ordering step) of the last join_asof call on this device"""
+        r, g, p = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_join_asof_last(self.ctx, C.byref(r), C.byref(g), C.byref(p)), "aqg_join_asof_last")
+        return r.value, g.value, p.value
 
     def gather_fill(self, x, idx, fill=None):
         """out[i] = fill where idx[i] == 0xFFFFFFFF, else x[idx[i]]; fill None = zero bytes (aqg_gather_fill)"""

@@ -58,6 +58,7 @@ struct aqg_ctx {
     size_t distinct_pairs_cap = 0;
     struct aqg_groupby* distinct_scratch = nullptr;
     uint32_t join_routes = 0, join_groups = 0, join_slots = 0;   // aqg_join_keys_*: form and route, distinct build tuples and table slots of the last call (aqg_join_last)
+    uint32_t asof_routes = 0, asof_groups = 0, asof_passes = 0;   // aqg_join_asof: routes, distinct build tuples and the ordering step's digit passes of the last call (aqg_join_asof_last)
     uint32_t str_route = 0, str_mismatch = 0;    // aqg_str_encode: the route of the last call and whether its verify kernel saw a mismatch (aqg_str_encode_last)
     // pinned host staging for small results
     void* host_stage = nullptr;

@@ -236,6 +236,27 @@ int join_keys_core(aqg_ctx* ctx, int kind, int nkeys, const int* dts, const void
 
 } // namespace
 
+// ---- the tuple probe for the joins that search behind it (join_tail.hpp; asof.hip) ------------------------------------------------
+int aqg_jk_check(aqg_ctx* ctx, int nkeys, const int* dts, const void* const* bk, uint32_t nb, const void* const* pk, uint32_t np) {
+    JKCols kb, kp;
+    return check_args(ctx, nkeys, dts, bk, nb, pk, np, &kb, &kp);
+}
+size_t aqg_jk_table_bytes(int nkeys, const int* dts, uint32_t G) {
+    JKCols kc;
+    return jk_plan(nkeys, dts, nullptr, &kc) == AQG_OK ? table_bytes(kc, G) : 0;
+}
+int aqg_jk_probe_gid(aqg_ctx* ctx, int nkeys, const int* dts, const void* const* bk, const void* const* pk, uint32_t np, aqg_groupby* gb, uint32_t* gid) {
+    JKCols kb, kp;
+    AQG_TRY(jk_plan(nkeys, dts, bk, &kb));
+    AQG_TRY(jk_plan(nkeys, dts, pk, &kp));
+    JKTable t{};
+    AQG_TRY(make_table(ctx, kb, gb, &t));
+    const uint32_t last[3] = {ctx->join_routes, ctx->join_groups, ctx->join_slots};        // aqg_join_last keeps describing the last aqg_join_keys_* call
+    const int rc = launch_probe(ctx, kp, np, t, nullptr, gid);
+    ctx->join_routes = last[0]; ctx->join_groups = last[1]; ctx->join_slots = last[2];
+    return rc;
+}
+
 extern "C" {
 
 int aqg_join_keys_count(aqg_ctx* ctx, int kind, int nkeys, const int* key_dtypes, const void* const* build_keys, uint32_t nb,

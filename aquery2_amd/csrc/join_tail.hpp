@@ -36,5 +36,12 @@ size_t aqg_join_tail_ws_bytes(uint32_t np);
 int aqg_join_tail(aqg_ctx* ctx, int kind, const uint32_t* gid, uint32_t np, const JoinBuild& build, uint32_t* probe_rows, uint32_t* build_rows,
                   uint64_t capacity, uint64_t* m_host, const char* who);
 
+// join_keys.hip: the tuple probe for the joins that search behind it (asof.hip).  aqg_jk_check: the argument, dtype, tuple-width and
+// row-count checks of aqg_join_keys_lookup.  aqg_jk_probe_gid: gid[i] = the group of `gb` (the grouped build side) whose tuple equals
+// probe row i, else NONE; its table comes from the caller's workspace (reset, sized with aqg_jk_table_bytes beside the caller's own needs).
+int aqg_jk_check(aqg_ctx* ctx, int nkeys, const int* dts, const void* const* bk, uint32_t nb, const void* const* pk, uint32_t np);
+size_t aqg_jk_table_bytes(int nkeys, const int* dts, uint32_t G);
+int aqg_jk_probe_gid(aqg_ctx* ctx, int nkeys, const int* dts, const void* const* bk, const void* const* pk, uint32_t np, aqg_groupby* gb, uint32_t* gid);
+
 // join.hip: aqg_join_lookup, which also says what it ran (the slots of its table over the build ROWS, and the route of its probe)
 int aqg_join_lookup_routed(aqg_ctx* ctx, int t, const void* bk, uint32_t nb, const void* pk, uint32_t np, uint32_t* out, uint32_t* table_slots, bool* lds);

@@ -507,6 +507,38 @@ int aqg_join_last(aqg_ctx* ctx, uint32_t* routes, uint32_t* build_groups, uint32
 int aqg_join_tuple_slots(int nkeys, const int* key_dtypes, const void* const* host_keys, uint32_t n, uint32_t table_slots,
                          uint32_t* slots_out_host);
 
+/* ---- as-of join: the nearest earlier or later build row per key tuple (the contract: tests/asof_model.py)
+ * For each probe row, the build row of the same key tuple whose `on` value is nearest at or before (BACKWARD) or at or after
+ * (FORWARD) the probe row's: for each trade the last quote of its symbol.  The reference has no counterpart.
+ * Equality keys: nkeys in 0..8; dtypes, tuple limits and equality exactly those of aqg_join_keys_* (-0.0 == +0.0, a NaN key equals
+ * nothing, no reserved values, strings through one dictionary's codes).  nkeys == 0 is a pure as-of on `on`: key_dtypes and both key
+ * lists may be NULL, every row is in one group and no hash probe runs.  Dtype and tuple-width errors return as they do from
+ * aqg_join_keys_lookup, with nothing written.
+ * `on`: one dtype for both sides, INT8/16/32/64, UINT8/16/32/64, FLOAT or DOUBLE; anything else (BOOL, 128-bit, DATE / TIME /
+ * TIMESTAMP included) is AQG_ERR_DTYPE with nothing written.  Order is numeric; -0.0 == +0.0.  A probe row whose `on` is NaN has no
+ * partner; a build row whose `on` is NaN is nobody's partner.
+ * Result, with B(i) = the build rows whose key tuple equals probe row i's and whose `on` is not NaN:
+ *   BACKWARD  the row of B(i) with the largest `on` <= probe `on` (< under AQG_ASOF_STRICT); among rows of that `on` the HIGHEST row id
+ *   FORWARD   the row of B(i) with the smallest `on` >= probe `on` (> under AQG_ASOF_STRICT); among rows of that `on` the LOWEST row id
+ *   no such row: 0xFFFFFFFF (the missing-row marker of aqg_gather_fill)
+ * -- the ties of kdb's `aj` and of pandas `merge_asof`.  Neither side needs to be sorted; a build side whose `on` is already
+ * non-decreasing (NaNs, if any, last) is noticed and spared the sort on `on`.  nb == 0: all 0xFFFFFFFF; np == 0: nothing written,
+ * AQG_OK.  `direction` or `flags` outside the enums, a NULL column with rows, an output overlapping an input: AQG_ERR_ARG; row
+ * counts beyond AQG_MAX_ROWS likewise.  Returns after the stream has drained and the call's temporaries are released.
+ * aqg_join_asof_last (diagnostic, like aqg_join_last): the routes of the last call on the context -- LDS / HBM: the search read the
+ * ordered build side from LDS / in place; NOKEYS: no key columns, no hash probe; PRESORTED: the build side's `on` was in order --
+ * the distinct build tuples (1 without key columns) and the digit passes the ordering step ran (aqg_sort_last_passes; 0 when
+ * nothing was sorted).  All zero when no probe ran (an empty side, an argument error).                                              */
+enum { AQG_ASOF_BACKWARD = 0, AQG_ASOF_FORWARD = 1 };
+enum { AQG_ASOF_STRICT = 1 };                       /* flags */
+int aqg_join_asof(aqg_ctx* ctx, int direction, int flags,
+                  int nkeys, const int* key_dtypes,
+                  const void* const* build_keys, const void* build_on, uint32_t nb,
+                  const void* const* probe_keys, const void* probe_on, uint32_t np,
+                  int on_dtype, uint32_t* build_row_of_probe);
+enum { AQG_ASOF_ROUTE_LDS = 1, AQG_ASOF_ROUTE_HBM = 2, AQG_ASOF_ROUTE_NOKEYS = 4, AQG_ASOF_ROUTE_PRESORTED = 8 };
+int aqg_join_asof_last(aqg_ctx* ctx, uint32_t* routes, uint32_t* build_groups, uint32_t* sort_passes);
+
 /* ---- the exchange step of row-sharded group-bys -------------------------------------------------
  * Tables shard by row range, one process per GPU; every shard groups its own rows and the shards' group tables are merged
  * by ONE all_gather (RCCL) of a fixed-size payload followed by a re-aggregation.  Because shards are contiguous row
