@@ -50,6 +50,14 @@ QUANTILE_PROTOTYPES = {
     "aqg_grouped_quantiles": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
     "aqg_grouped_quantiles_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
 }
+# ctypes prototypes of the moving-quantile entries (applied by load_library)
+WINQ_MAX_W = 1024
+WINQ_PROTOTYPES = {
+    "aqg_window_quantiles": [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "aqg_grouped_window_quantiles": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_grouped_window_quantiles_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_window_quantiles_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 # ctypes prototypes of the count-distinct entries (applied by load_library)
 DISTINCT_PROTOTYPES = {
     "aqg_count_distinct": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)],
@@ -116,7 +124,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -704,6 +712,34 @@ class Device:
         fn = self.lib.aqg_grouped_quantiles_flat if flat else self.lib.aqg_grouped_quantiles
         self._chk(fn(self.ctx, gb.h, which, nq, na, den, xd.tag, xd.ptr, out.ptr), "aqg_grouped_quantiles")
         return out if keep else out.to_host().reshape(G, nq)
+
+    # -- moving quantiles (rank tracking over every row's window: include/aqg.h, moving quantiles section)
+    def window_quantiles(self, x, nums, den, w, which=SEL_LOWER, keep=False, out=None):
+        """the rows of rank floor (SEL_LOWER) / ceil (SEL_UPPER) of nums[j] * (len - 1) / den of every row's window (the last
+        min(w, i + 1) rows) in ascending order: a (len(nums), n) array of the column's own dtype; nums = [1], den = 2 is medianw"""
+        xd = self._dev(x)
+        nq = len(nums)
+        na = (C.c_uint32 * max(1, nq))(*nums)
+        out = out if out is not None else self.empty(nq * xd.n, TAG2NP[xd.tag])
+        self._chk(self.lib.aqg_window_quantiles(self.ctx, which, nq, na, den, xd.tag, xd.ptr, xd.n, w, out.ptr), "aqg_window_quantiles")
+        return out if keep else out.to_host().reshape(nq, xd.n)
+
+    def grouped_window_quantiles(self, gb, x, nums, den, w, which=SEL_LOWER, flat=False, keep=False, out=None):
+        """window_quantiles within every group of a build, a (len(nums), n) array in the flat layout: `x` in row layout, or
+        (flat=True) already in the flat layout"""
+        xd = self._dev(x)
+        nq = len(nums)
+        na = (C.c_uint32 * max(1, nq))(*nums)
+        out = out if out is not None else self.empty(nq * xd.n, TAG2NP[xd.tag])
+        fn = self.lib.aqg_grouped_window_quantiles_flat if flat else self.lib.aqg_grouped_window_quantiles
+        self._chk(fn(self.ctx, gb.h, which, nq, na, den, xd.tag, xd.ptr, w, out.ptr), "aqg_grouped_window_quantiles")
+        return out if keep else out.to_host().reshape(nq, xd.n)
+
+    def window_quantiles_last(self):
+        """(rows a workgroup owns, halo rows in front of them) of the last window_quantiles / grouped_window_quantiles call"""
+        t, h = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_window_quantiles_last(self.ctx, C.byref(t), C.byref(h)), "aqg_window_quantiles_last")
+        return t.value, h.value
 
     # -- count distinct (include/aqg.h, count distinct section)
     def count_distinct(self, x):

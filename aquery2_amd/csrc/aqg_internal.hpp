@@ -59,6 +59,7 @@ struct aqg_ctx {
     struct aqg_groupby* distinct_scratch = nullptr;
     uint32_t join_routes = 0, join_groups = 0, join_slots = 0;   // aqg_join_keys_*: form and route, distinct build tuples and table slots of the last call (aqg_join_last)
     uint32_t asof_routes = 0, asof_groups = 0, asof_passes = 0;   // aqg_join_asof: routes, distinct build tuples and the ordering step's digit passes of the last call (aqg_join_asof_last)
+    uint32_t winq_tile = 0, winq_halo = 0;       // aqg_window_quantiles*: rows per workgroup and halo rows of the last call (aqg_window_quantiles_last)
     uint32_t str_route = 0, str_mismatch = 0;    // aqg_str_encode: the route of the last call and whether its verify kernel saw a mismatch (aqg_str_encode_last)
     // pinned host staging for small results
     void* host_stage = nullptr;

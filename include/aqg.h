@@ -301,6 +301,39 @@ int aqg_quantiles(aqg_ctx* ctx, int which, uint32_t nq, const uint32_t* num_host
 int aqg_grouped_quantiles(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* x, void* out_dev);
 int aqg_grouped_quantiles_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* xflat, void* out_dev);
 
+/* ---- moving quantiles ----------------------------------------------------------
+ * The windowed order statistics beside minw / maxw / avgw / varw: `medianw(21, price)` by symbol, a rolling p95 of a latency column --
+ * up to AQG_QUANTILES_MAX ranks of every row's window in one pass.
+ * Window: that of row i is rows [i - w + 1, i] of its SLICE -- the whole column, or the row's group in the flat layout -- clamped at the
+ * slice's first row: len = min(w, predecessors of i in the slice + 1), the growing prefix of sumw / minw.
+ * Rank: quantile j of row i is the row of rank r_j of that window in ascending order -- the order of aqg_median and of aqg_sort_rows
+ * under AQG_ORDER_ASC (-0.0 and +0.0 one value, every NaN one value above +inf) -- with
+ *   r_j = floor(num[j] * (len - 1) / den)   AQG_SEL_LOWER
+ *   r_j = ceil (num[j] * (len - 1) / den)   AQG_SEL_UPPER
+ * exact (unsigned 64-bit arithmetic on the device; nothing about the ranks comes from or goes to the host but num and den).  num = 1,
+ * den = 2, AQG_SEL_LOWER is the moving median, `medianw`; num[j] == 0 is minw, num[j] == den maxw; w == 1 returns the input; a window
+ * that is its whole slice gives aqg_quantiles of that slice.  num may come in any order and may repeat.
+ * Result: nq planes of n elements of the column's own dtype `t`, out[j * n + i] answers num[j] for row i; the grouped forms in the flat
+ * layout, like aqg_grouped_scan.  AN ELEMENT OF THE WINDOW bit for bit, with the median's two caveats and no others: when the rank lands
+ * on a zero of a window that holds both zeros, which zero comes back is unspecified; when it lands among the NaNs, some NaN comes back.
+ * Errors: 1 <= nq <= AQG_QUANTILES_MAX, den >= 1, num[j] <= den, w >= 1, else AQG_ERR_ARG.  The effective window is min(w, n); beyond
+ * AQG_WINQ_MAX_W rows it returns AQG_ERR_ARG: the work is O(w) per row, a longer window wants another algorithm (unbuilt, DESIGN.md
+ * section 4.14) -- the limit is a property of the interface, not a measurement.  `out` overlapping `x`: AQG_ERR_ARG.  Dtypes: those of
+ * aqg_median; anything else returns AQG_ERR_DTYPE.  Every error returns with nothing written.  n == 0 or G == 0: AQG_OK.
+ *   aqg_window_quantiles               the whole column
+ *   aqg_grouped_window_quantiles       every group's rows, x in ROW layout (brought into the flat layout in workspace, once whatever nq is)
+ *   aqg_grouped_window_quantiles_flat  the same over a column already in the FLAT LAYOUT of the build
+ * The grouped forms need a handle of aqg_groupby_build (a handle of aqg_groupby_agg: AQG_ERR_ARG, as the median).  The input is never
+ * modified.  Asynchronous on the context's stream, no host round trip, scratch from the context workspace, no allocation in steady
+ * state; two launches (the rank table and the windows) whatever n, G, w and nq are, the row-layout form adds the flatten.
+ * aqg_window_quantiles_last: the rows a workgroup owns (its tile) and the rows in front of a tile it reads as well (the halo, effective
+ * w - 1) of the last such call on this context -- a diagnostic: the tests put slice starts on the kernel's real tile edges with it.   */
+enum { AQG_WINQ_MAX_W = 1024 };
+int aqg_window_quantiles(aqg_ctx* ctx, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* x, uint32_t n, uint32_t w, void* out_dev);
+int aqg_grouped_window_quantiles(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* x, uint32_t w, void* out_flat_dev);
+int aqg_grouped_window_quantiles_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* xflat, uint32_t w, void* out_flat_dev);
+int aqg_window_quantiles_last(aqg_ctx* ctx, uint32_t* tile_rows, uint32_t* halo_rows);
+
 /* ---- count distinct ----------------------------------------------------------
  * `count(distinct x)`: the generator emits `(x).distinct_size()` (common/types.py:271-277), under GROUP BY `(x[val]).distinct_size()`
  * inside the generated loop (engine/ast.py:749-784).  Replaces vector_type::distinct_size (server/vector_type.hpp:153-174) and

@@ -4,10 +4,12 @@
 // reduced / scanned by one HIP kernel through the C-ABI; scalars fall through to the identity overloads
 // at the bottom exactly like the reference's.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <initializer_list>
 #include <limits>
 #include <utility>
+#include <vector>
 
 #include "gc.h"
 #include "types.h"
@@ -98,6 +100,54 @@ template <class T, template <typename...> class VT> inline void device_quantiles
         if (rt.deferred_quantiles(arr.container, arr.size, which, den, nums + b, m, out + b)) continue;
         dev::In in(arr.container, (size_t)arr.size * sizeof(T), arr.capacity == 0);     // not a deferred `col[vecs[g]]`: this very vector
         dev::check(aqg_quantiles(rt.ctx(), which, m, nums + b, den, dev::tag_of<T>::value, in.d, arr.size, out + b), "aqg_quantiles");
+    }
+}
+// ret[i] = the row of rank floor (AQG_SEL_LOWER) / ceil (AQG_SEL_UPPER) of num (len - 1) / den of the last len = min(w, i + 1) elements of
+// arr in ascending order (include/aqg.h, moving quantiles section).  A per-group temporary of the generated loop is answered for ALL groups
+// by one aqg_grouped_window_quantiles_flat (Runtime::vcol_window_quantile) and `ret` becomes this group's slice of that result, exactly as
+// device_scan does; any other vector goes through aqg_window_quantiles.
+// THE SLOW PATH: an effective window min(w, arr.size) above AQG_WINQ_MAX_W is beyond the device call (O(w) per row there; the wide-window
+// algorithm is unbuilt).  The vector is brought to the host and every window answered by std::nth_element on a
+// copy, under the same order (NaNs above +inf, the two zeros one value): O(w) per row on one core.
+template <class T, template <typename...> class VT, class Ret> inline void device_window_quantile(int which, uint32_t w, uint32_t num, uint32_t den, const VT<T>& arr, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    using E = std::remove_cv_t<T>;
+    static_assert(std::is_same_v<RT, E>, "medianw / quantilew: the result holds elements of the input");
+    auto& rt = dev::Runtime::get();
+    const uint32_t n = arr.size;
+    if (n == 0) return;
+    if (w <= (uint32_t)AQG_WINQ_MAX_W) {
+        if (dev::Entry* e = rt.deferred_at(arr.container)) {
+            dev::GroupCtx* gc = e->dgroup;
+            const uint32_t g = e->dg;
+            const int r = rt.vcol_window_quantile(gc, e->dv, w, which, num, den);
+            rt.defer_slice(ret.container, (size_t)n * sizeof(RT), gc, g, r);
+            if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+            return;
+        }
+    }
+    if ((w < n ? w : n) <= (uint32_t)AQG_WINQ_MAX_W) {
+        dev::In in(arr.container, (size_t)n * sizeof(T), arr.capacity == 0);
+        void* dout = rt.result(ret.container, (size_t)n * sizeof(RT));
+        dev::check(aqg_window_quantiles(rt.ctx(), which, 1, &num, den, dev::tag_of<E>::value, in.d, n, w, dout), "aqg_window_quantiles");
+        if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+        return;
+    }
+    if (den < 1 || num > den || (which != AQG_SEL_LOWER && which != AQG_SEL_UPPER)) dev::check(AQG_ERR_ARG, "medianw / quantilew: num / den");
+    const E* x = arr.begin();                                  // (host access: downloads a device result)
+    rt.forget_range(ret.container, (size_t)n * sizeof(RT));    // (host memory written here: no device result stands behind it)
+    auto before = [](const E& a, const E& b) {
+        if constexpr (std::is_floating_point_v<E>) { if (b != b) return a == a; if (a != a) return false; }
+        return a < b;
+    };
+    std::vector<E> win(w < n ? w : n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t len = i + 1 < w ? i + 1 : w;
+        std::copy(x + (i + 1 - len), x + i + 1, win.begin());
+        const uint64_t p = (uint64_t)num * (len - 1);
+        const uint32_t k = (uint32_t)(p / den + (which == AQG_SEL_UPPER && p % den != 0 ? 1u : 0u));
+        std::nth_element(win.begin(), win.begin() + k, win.begin() + len, before);
+        ret.container[i] = win[k];
     }
 }
 } // namespace aq
@@ -253,6 +303,18 @@ AQ_WINDOW(ratiow, AQG_SCAN_RATIOW, types::GetFPType<T>)
 #undef AQ_SCAN
 #undef AQ_WINDOW
 
+// medianw(w, v) / quantilew(w, num, den, v): the moving median / the moving quantile num / den of the last min(w, i + 1) elements -- the
+// LOWER rank, an element of the window (include/aqg.h, moving quantiles section); they fill the hole between minw / maxw and avgw / varw,
+// the count first.  The reference's header has neither.  medianw(w, v) is quantilew(w, 1, 2, v).
+template <class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+void quantilew(uint32_t w, uint32_t num, uint32_t den, const VT<T>& arr, Ret& ret) { aq::device_window_quantile(AQG_SEL_LOWER, w, num, den, arr, ret); }
+template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+inline decayed_t<VT, T> quantilew(uint32_t w, uint32_t num, uint32_t den, const VT<T>& arr) { decayed_t<VT, T> ret(arr.size); aq::device_window_quantile(AQG_SEL_LOWER, w, num, den, arr, ret); return ret; }
+template <class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+void medianw(uint32_t w, const VT<T>& arr, Ret& ret) { aq::device_window_quantile(AQG_SEL_LOWER, w, 1, 2, arr, ret); }
+template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
+inline decayed_t<VT, T> medianw(uint32_t w, const VT<T>& arr) { decayed_t<VT, T> ret(arr.size); aq::device_window_quantile(AQG_SEL_LOWER, w, 1, 2, arr, ret); return ret; }
+
 template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
 inline decayed_t<VT, types::GetFPType<T>> ratios(const VT<T>& arr) { return ratiow(1, arr); }
 template <class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
@@ -266,12 +328,13 @@ template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constex
 AQ_SCALAR_ID(max) AQ_SCALAR_ID(min) AQ_SCALAR_ID(avg) AQ_SCALAR_ID(sum) AQ_SCALAR_ID(maxs) AQ_SCALAR_ID(mins) AQ_SCALAR_ID(avgs)
 AQ_SCALAR_ID(sums) AQ_SCALAR_ID(last) AQ_SCALAR_ID(first) AQ_SCALAR_ID(prev) AQ_SCALAR_ID(aggnext) AQ_SCALAR_ID(median)
 AQ_SCALAR_ZERO(var) AQ_SCALAR_ZERO(vars) AQ_SCALAR_ZERO(stddev) AQ_SCALAR_ZERO(stddevs) AQ_SCALAR_ZERO(deltas)
-AQ_SCALAR_WID(maxw) AQ_SCALAR_WID(minw) AQ_SCALAR_WID(avgw) AQ_SCALAR_WID(sumw) AQ_SCALAR_WID(maxk) AQ_SCALAR_WID(mink)
+AQ_SCALAR_WID(maxw) AQ_SCALAR_WID(minw) AQ_SCALAR_WID(avgw) AQ_SCALAR_WID(sumw) AQ_SCALAR_WID(maxk) AQ_SCALAR_WID(mink) AQ_SCALAR_WID(medianw)
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T varw(uint32_t, const T&) { return 0; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T stddevw(uint32_t, const T&) { return 0; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T ratiow(uint32_t, const T&) { return 1; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T ratios(const T&) { return 1; }
 template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T quantile(uint32_t, uint32_t, const T& v) { return v; }
+template <class T, std::enable_if_t<std::is_arithmetic_v<T>>* = nullptr> constexpr T quantilew(uint32_t, uint32_t, uint32_t, const T& v) { return v; }
 #undef AQ_SCALAR_ID
 #undef AQ_SCALAR_ZERO
 #undef AQ_SCALAR_WID

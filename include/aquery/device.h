@@ -242,6 +242,22 @@ public:
         if (rc != AQG_OK) die("aqg_grouped_scan_flat", rc, ctx_);
         return vcol_new(c, key, r);
     }
+    // quantile num / den (which: AQG_SEL_LOWER / UPPER) of the window of w rows that ends at every row of every group's slice (medianw /
+    // quantilew of a per-group temporary): ONE aqg_grouped_window_quantiles_flat over the flat column, whatever the number of groups
+    size_t grouped_window_quantile_calls = 0;   // aqg_grouped_window_quantiles_flat calls made so far (the tests count them)
+    int vcol_window_quantile(GroupCtx* c, int v, uint32_t w, int which, uint32_t num, uint32_t den) {
+        const std::array<uint64_t, 6> key{4, (uint64_t)which, (uint64_t)v, w, num, den};
+        auto it = c->memo.find(key);
+        if (it != c->memo.end()) return it->second;
+        VCol r; r.layout = 1; r.tag = c->vcols[v].tag;
+        const void* xf = vcol_flat_ptr(c, v);
+        int rc = aqg_malloc(ctx(), (size_t)c->n * esz(r.tag) + 16, &r.dptr);
+        if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+        ++grouped_window_quantile_calls;
+        rc = aqg_grouped_window_quantiles_flat(ctx_, c->handle, which, 1, &num, den, r.tag, xf, w, r.dptr);
+        if (rc != AQG_OK) die("aqg_grouped_window_quantiles_flat", rc, ctx_);
+        return vcol_new(c, key, r);
+    }
     // l OP r of two columns of the grouping: in row order when both are (one pass over the whole columns), else in the flat layout
     int vcol_ewise(GroupCtx* c, int op, int l, int r, int ot) {
         const std::array<uint64_t, 6> key{2, (uint64_t)op, (uint64_t)l, (uint64_t)r, (uint64_t)ot, 0};
