@@ -1,5 +1,6 @@
-// select_dev.hpp -- what select.hip (median), topk.hip (top-k) and distinct.hip (count distinct) share: the workgroup scan, the element size
-// of a dtype they accept, and the offsets {0, n} that turn a whole column into the one group of a flat call.
+// select_dev.hpp -- what the radix selections (select.hip, topk.hip, quantile.hip and window_quantile.hip, through select_radix.hpp) and
+// distinct.hip (count distinct) share: the workgroup scan, the element size of a dtype they accept, and the offsets {0, n} that turn a
+// whole column into the one group of a flat call.
 #pragma once
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"

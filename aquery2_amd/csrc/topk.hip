@@ -3,7 +3,7 @@
 //
 // A selection, not a sort: rows are never moved.  Every row is compared through its KEY: the order-preserving image of key_image.hpp under
 // AQG_ORDER_ASC, its complement under AQG_ORDER_DESC, so that both orders are "the m = min(k, c) smallest keys of the c rows, ties by
-// ascending position".  The three routes and their thresholds are those of select.hip (select_dev.hpp), chosen per group on the device:
+// ascending position".  The three routes and their thresholds are those of select.hip (select_radix.hpp), chosen per group on the device:
 //   SMALL  a workgroup stages the keys of a tile of flat positions in LDS and its wavefronts rank every group that starts in the tile by
 //          comparison counting (ties by position); a row of rank r < m stores itself at slot r.  One launch, no threshold search.
 //   GROUP  one workgroup owns one group: the MSD radix selection of select.hip finds the key T of rank m - 1 and, on the way, how many of
@@ -15,8 +15,7 @@
 //          No workgroup waits for another.
 // Elements are written as read back through their position, so every value is an element of the input bit for bit whatever its image.
 // Which of the rows equal to T are taken when there are more than `need` depends on the order the wavefronts arrive in.
-#include "groupby_handle.hpp"
-#include "select_radix.hpp"
+#include "select_host.hpp"
 
 namespace {
 using namespace selradix;
@@ -26,38 +25,6 @@ static_assert(KMAX % SB == 0 && SMALL_CAP <= KMAX, "the candidates of a group ar
 constexpr uint32_t DONE_KEY = 1, DONE_ALL = 3;          // SelState::done of a SPLIT group: T is st.prefix / every row is taken
 
 __device__ inline uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
-// rows [lo, hi) (lo < hi) of x through f(raw, position, live), every lane of the workgroup calling f the same number of times: 16-byte loads
-// over the aligned middle of the slice, UNR of them in flight per lane, the elements in front of and behind it one lane each (as hist_rows)
-template <class U, class F>
-__device__ inline void sweep_rows(const U* __restrict__ x, uint32_t lo, uint32_t hi, F&& f) {
-    constexpr uint32_t V = 16 / sizeof(U);
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(x + lo) & 15);
-    uint32_t hl = mis ? (16 - mis) / (uint32_t)sizeof(U) : 0u;
-    if (hl > hi - lo) hl = hi - lo;
-    const uint32_t a0 = lo + hl, nvec = (hi - a0) / V, ts = a0 + nvec * V, tl = hi - ts;
-    {
-        const bool live = threadIdx.x < hl + tl;
-        const uint32_t e = threadIdx.x < hl ? lo + threadIdx.x : ts + (threadIdx.x - hl);
-        const uint32_t p = live ? e : lo;
-        f(x[p], p, live);
-    }
-    const vec16<U>* xv = reinterpret_cast<const vec16<U>*>(x + a0);
-    for (uint32_t vb = 0; vb < nvec; vb += SB * UNR) {
-        vec16<U> r[UNR];
-        bool live[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const uint32_t vi = vb + u * SB + threadIdx.x;
-            live[u] = vi < nvec;
-            r[u] = xv[live[u] ? vi : nvec - 1];
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u)
-#pragma unroll
-            for (uint32_t e = 0; e < V; ++e) f(r[u].v[e], a0 + (vb + u * SB + threadIdx.x) * V + e, live[u]);
-    }
-}
 
 // the lanes of a wavefront with `p` set take consecutive numbers from *counter (one atomic per wavefront; others: 0xFFFFFFFF).
 // *end: one past the last number this wavefront took (the same in every lane; 0 when no lane asked)
@@ -118,120 +85,33 @@ __device__ inline void rank_emit(const U* __restrict__ x, const uint32_t* cand, 
     }
 }
 
-// ---- routing: one lane per group (as select_classify_kernel; the rank wanted is the last of the m kept rows) -------------------------------
+// ---- routing: one lane per group (the rank wanted is the last of the m kept rows) ------------------------------------------------------------
 __global__ void __launch_bounds__(SB) topk_classify_kernel(const uint32_t* __restrict__ off, uint32_t G, uint32_t small_max, uint32_t split_min, uint32_t k, int bits,
                                                             uint32_t* __restrict__ tile_first, uint32_t* __restrict__ glist, SelState* __restrict__ sst, uint32_t* __restrict__ ctl) {
-    uint32_t mask = 0;
-    for (uint32_t g = blockIdx.x * SB + threadIdx.x; g < G; g += gridDim.x * SB) {
-        const uint32_t lo = off[g], hi = off[g + 1], c = hi - lo;
-        if (c == 0) continue;
-        if (c <= small_max) {
-            mask |= ROUTE_SMALL;
-            bool first = g == 0;
-            if (!first) { const uint32_t plo = off[g - 1], pc = lo - plo; first = plo / TILE != lo / TILE || pc > small_max || pc == 0; }
-            if (first) atomicMin(&tile_first[lo / TILE], g);
-        } else if (c < split_min) {
-            mask |= ROUTE_GROUP;
-            glist[atomicAdd(&ctl[CTL_NGROUP], 1u)] = g;
-        } else {
-            mask |= ROUTE_SPLIT;
-            SelState st{};
-            st.vand = ~0ull;
-            st.lo = lo; st.hi = hi; st.k = min_u32(k, c) - 1; st.gidx = g;
-            st.shift = (uint32_t)bits - 8;
-            st.done = c <= k ? DONE_ALL : 0u;
-            sst[atomicAdd(&ctl[CTL_NSPLIT], 1u)] = st;
-        }
-    }
-    mask = wave_reduce(mask, OpOr{});
-    if (lane_id() == 0 && mask) {
-        atomicOr(&ctl[CTL_ROUTES], mask);
-        if (mask & ROUTE_SMALL) atomicMax(&ctl[CTL_PASSES], 1u);       // ranking by comparison: one pass over the group
-    }
+    classify_groups(off, G, small_max, split_min, tile_first, glist, ctl, [&](uint32_t g, uint32_t lo, uint32_t hi, uint32_t c, uint32_t s) {
+        SelState st = split_state(lo, hi, min_u32(k, c) - 1, g, (uint32_t)bits);
+        st.done = c <= k ? DONE_ALL : 0u;
+        sst[s] = st;
+    });
 }
 
 // ---- SMALL ----------------------------------------------------------------------------------------------------------------------------------
 template <class U, int KIND>
 __global__ void __launch_bounds__(SB) topk_small_kernel(const U* __restrict__ x, uint32_t n, const uint32_t* __restrict__ off, uint32_t G,
                                                          const uint32_t* __restrict__ tile_first, uint32_t small_max, uint32_t k, U* __restrict__ vals, uint32_t* __restrict__ pos_out) {
-    constexpr uint32_t V = 16 / sizeof(U), ROWS = TILE + SMALL_CAP, PER = (ROWS / V + SB - 1) / SB;
-    __shared__ U img[ROWS];
-    __shared__ uint32_t goff[TILE + 2];
-    __shared__ uint32_t s_ng;
-    const uint32_t g0 = tile_first[blockIdx.x];
-    if (g0 == 0xFFFFFFFFu) return;
-    const uint32_t tbeg = blockIdx.x * TILE, tend = n - tbeg < TILE ? n : tbeg + TILE;
-    if (threadIdx.x == 0) s_ng = 0xFFFFFFFFu;
-    __syncthreads();
-    // offsets of the groups that start in this tile, and the end of the last one
-    for (uint32_t base = 0;; base += SB) {
-        const uint32_t i = base + threadIdx.x, gi = g0 + i < G ? g0 + i : G;
-        const uint32_t o = off[gi];
-        if (i < TILE + 2) goff[i] = o;
-        const bool beyond = o >= tend || gi == G;
-        if (beyond) atomicMin(&s_ng, i);
-        if (__syncthreads_or(beyond)) break;
-    }
-    const uint32_t ng = s_ng;
-    auto put = [&](uint32_t gi, uint32_t slot, uint32_t p) {
-        const size_t o = (size_t)(g0 + gi) * k + slot;
+    auto put = [&](uint32_t g, uint32_t slot, uint32_t p) {
+        const size_t o = (size_t)g * k + slot;
         vals[o] = x[p];
         if (pos_out) pos_out[o] = p;
     };
-    // one or two rows: a lane each, from the column itself
-    bool any = false;
-    for (uint32_t gi = threadIdx.x; gi < ng; gi += SB) {
-        const uint32_t lo = goff[gi], c = goff[gi + 1] - lo;
-        if (c > small_max || c == 0) continue;
-        if (c == 1) put(gi, 0, lo);
-        else if (c == 2) {
-            const uint32_t second = image_of<U, KIND>(x[lo + 1]) < image_of<U, KIND>(x[lo]) ? 0u : 1u;     // (equal keys: positions ascend)
-            put(gi, 0, lo + 1 - second);
-            if (k > 1) put(gi, 1, lo + second);
-        } else any = true;
-    }
-    if (!__syncthreads_or(any)) return;
-    // keys of rows [tbeg, tbeg + ROWS) -> LDS
-    const uint32_t L = n - tbeg < ROWS ? n - tbeg : ROWS;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && L >= V) {
-        const uint32_t nvec = L / V;
-        const vec16<U>* xv = reinterpret_cast<const vec16<U>*>(x + tbeg);
-        vec16<U> r[PER];
-#pragma unroll
-        for (uint32_t u = 0; u < PER; ++u) { const uint32_t vi = u * SB + threadIdx.x; r[u] = xv[vi < nvec ? vi : nvec - 1]; }
-#pragma unroll
-        for (uint32_t u = 0; u < PER; ++u) {
-            const uint32_t vi = u * SB + threadIdx.x;
-            if (vi < nvec) {
-#pragma unroll
-                for (uint32_t e = 0; e < V; ++e) img[vi * V + e] = image_of<U, KIND>(r[u].v[e]);
-            }
-        }
-        for (uint32_t i = nvec * V + threadIdx.x; i < L; i += SB) img[i] = image_of<U, KIND>(x[tbeg + i]);
-    } else {
-#pragma unroll 4
-        for (uint32_t i = threadIdx.x; i < L; i += SB) img[i] = image_of<U, KIND>(x[tbeg + i]);
-    }
-    __syncthreads();
-    // a wavefront per group: rank of every row = rows that sort before it (ties by position); the rows of rank below m are the answer
-    const uint32_t lane = lane_id();
-    for (uint32_t gi = wave_id(); gi < ng; gi += NWV) {
-        const uint32_t lo = goff[gi], c = goff[gi + 1] - lo;
-        if (c < 3 || c > small_max) continue;
-        const uint32_t base = lo - tbeg, m = min_u32(k, c);
-        for (uint32_t eb = 0; eb < c; eb += 64) {
-            const bool live = eb + lane < c;
-            const uint32_t ii = live ? eb + lane : c - 1;
-            const U mine = img[base + ii];
-            uint32_t less = 0;
-#pragma unroll 4
-            for (uint32_t j = 0; j < c; ++j) {
-                const U v = img[base + j];
-                less += (v < mine) | ((v == mine) & (j < ii));
-            }
-            if (live && less < m) put(gi, less, lo + ii);
-        }
-    }
+    small_tile<U, KIND>(
+        x, n, off, G, tile_first, small_max,
+        [&](uint32_t g, uint32_t lo, uint32_t c, bool a_first) {                                     // (equal keys: positions ascend)
+            put(g, 0, a_first ? lo : lo + 1);
+            if (c == 2 && k > 1) put(g, 1, a_first ? lo + 1 : lo);
+        },
+        [&](uint32_t c) { return min_u32(k, c); },
+        [&](uint32_t g, uint32_t lo, uint32_t m, uint32_t ii, uint32_t less) { if (less < m) put(g, less, lo + ii); });      // the rows of rank below m are the answer
 }
 
 // ---- GROUP ----------------------------------------------------------------------------------------------------------------------------------
@@ -252,29 +132,11 @@ __global__ void __launch_bounds__(SB) topk_group_kernel(const U* __restrict__ x,
         SelState st{};
         st.k = m - 1;
         st.shift = sizeof(U) * 8 - 8;
-        U T = 0;
         while (c > k) {                                                         // the key of rank m - 1; st.k ends as that rank among the rows equal to it
-            __syncthreads();
-            for (uint32_t j = 0; j < NHIST<U>; ++j) h[j * 256 + threadIdx.x] = 0;
-            if (threadIdx.x == 0) { s_and = ~0ull; s_or = 0ull; }
-            __syncthreads();
-            U vand = (U)~U(0), vor = 0;
-            hist_rows<U, KIND>(x, lo, hi, (U)st.prefix, (U)st.kmask, st.shift, h, vand, vor);
-            fold_and_or(vand, vor, &s_and, &s_or);
-            __syncthreads();
-            ++st.passes;
-            st.vand = s_and; st.vor = s_or;
-            if (st.vand == st.vor) { T = (U)st.vand; break; }                   // one candidate, or all of them equal
-            choose_bin(h[threadIdx.x], st.k, wsum, &sel);
-            if (both_digits_known<U>(st, sel.cnt, sel.total)) {
-                __syncthreads();
-                choose_bin(h[256 * (NHIST<U> - 1) + threadIdx.x], st.k, wsum, &sel);
-                T = (U)((st.vand & ~0xFFull) | sel.bin);
-                st.k -= sel.excl;
-                break;
-            }
-            if (sel_advance(st, sel.bin, sel.excl, sel.cnt, sel.total)) { T = (U)st.prefix; break; }
+            group_pass<U, KIND>(x, lo, hi, st, h, &s_and, &s_or);
+            if (digit_step<U>(st, h[threadIdx.x], h[256 * (NHIST<U> - 1) + threadIdx.x], wsum, &sel)) break;
         }
+        const U T = (U)st.prefix;
         __syncthreads();
         if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
         for (uint32_t i = threadIdx.x; i < m; i += SB) cand[i] = lo;
@@ -303,18 +165,7 @@ __global__ void __launch_bounds__(SB) topk_split_choose_kernel(SelState* __restr
         const uint32_t c = gh[threadIdx.x], c2 = gh[256 * (NHIST<U> - 1) + threadIdx.x];
         for (uint32_t j = 0; j < NHIST<U>; ++j) gh[j * 256 + threadIdx.x] = 0;
         ++st.passes;
-        bool done;
-        if (st.vand == st.vor) { st.prefix = st.vand; done = true; }
-        else {
-            choose_bin(c, st.k, wsum, &sel);
-            if (both_digits_known<U>(st, sel.cnt, sel.total)) {
-                __syncthreads();
-                choose_bin(c2, st.k, wsum, &sel);
-                st.prefix = (st.vand & ~0xFFull) | sel.bin;
-                st.k -= sel.excl;
-                done = true;
-            } else done = sel_advance(st, sel.bin, sel.excl, sel.cnt, sel.total);
-        }
+        const bool done = digit_step<U>(st, c, c2, wsum, &sel);
         if (threadIdx.x == 0) {
             if (done) st.done = DONE_KEY;
             st.vand = ~0ull; st.vor = 0ull;
@@ -364,74 +215,45 @@ size_t topk_ws_bytes(uint32_t n, uint32_t G, uint32_t k, SelSwitches sw) {
 }
 // the three routes over a column in the flat layout (workspace sized by topk_ws_bytes and not reset in here; the control words are zero)
 template <class U, int KIND>
-int run_topk(aqg_ctx* ctx, const void* xv, uint32_t n, const uint32_t* off, uint32_t G, uint32_t k, SelSwitches sw, void* valsv, uint32_t* pos_out) {
-    const U* x = static_cast<const U*>(xv);
+int run_topk(aqg_ctx* ctx, const SelInput& in, uint32_t k, SelSwitches sw, void* valsv, uint32_t* pos_out) {
+    const U* x = static_cast<const U*>(in.x);
     U* vals = static_cast<U*>(valsv);
     uint32_t* ctl = ctx->select_ctl;
-    const uint32_t ntiles = aqg_ceil_div(n, TILE), scap = split_cap(n, G, sw.split_min);
-    const uint32_t glcap = (n / (sw.small_max + 1) < G ? n / (sw.small_max + 1) : G) + 1;
-    const bool do_small = sw.small_max >= 1, do_group = n > sw.small_max && sw.split_min > sw.small_max + 1, do_split = n >= sw.split_min && n > sw.small_max;
-    uint32_t *tile_first, *glist, *ghist, *cur, *cand;
-    SelState* sst;
-    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles + 1, &tile_first));
-    AQG_TRY(aqg_ws_get(ctx, glcap, &glist));
-    AQG_TRY(aqg_ws_get(ctx, scap, &sst));
-    AQG_TRY(aqg_ws_get(ctx, (size_t)scap * 256 * NHIST<U>, &ghist));
-    AQG_TRY(aqg_ws_get(ctx, (size_t)scap * 2, &cur));
-    AQG_TRY(aqg_ws_get(ctx, (size_t)scap * k, &cand));
+    SelPlan p;
+    AQG_TRY(p.init(ctx, in.n, in.G, sw, NHIST<U>));
+    uint32_t *cur, *cand;
+    AQG_TRY(aqg_ws_get(ctx, (size_t)p.scap * 2, &cur));
+    AQG_TRY(aqg_ws_get(ctx, (size_t)p.scap * k, &cand));
     // the slots no row fills: zero bytes and the missing-row marker
-    AQG_HIP(ctx, hipMemsetAsync(vals, 0, (size_t)G * k * sizeof(U), ctx->stream));
-    if (pos_out) AQG_HIP(ctx, hipMemsetAsync(pos_out, 0xFF, (size_t)G * k * 4, ctx->stream));
-    if (do_small) AQG_HIP(ctx, hipMemsetAsync(tile_first, 0xFF, (size_t)ntiles * 4, ctx->stream));
-    if (do_split) {
-        AQG_HIP(ctx, hipMemsetAsync(ghist, 0, (size_t)scap * 1024 * NHIST<U>, ctx->stream));
-        AQG_HIP(ctx, hipMemsetAsync(cur, 0, (size_t)scap * 8, ctx->stream));
-        AQG_HIP(ctx, hipMemsetAsync(cand, 0, (size_t)scap * k * 4, ctx->stream));        // (a slot no row took would still be a position of the column)
+    AQG_HIP(ctx, hipMemsetAsync(vals, 0, (size_t)in.G * k * sizeof(U), ctx->stream));
+    if (pos_out) AQG_HIP(ctx, hipMemsetAsync(pos_out, 0xFF, (size_t)in.G * k * 4, ctx->stream));
+    if (p.do_split) {
+        AQG_HIP(ctx, hipMemsetAsync(cur, 0, (size_t)p.scap * 8, ctx->stream));
+        AQG_HIP(ctx, hipMemsetAsync(cand, 0, (size_t)p.scap * k * 4, ctx->stream));        // (a slot no row took would still be a position of the column)
     }
-    const unsigned ggrid = aqg_grid(ctx, G, SB, 1, 8);
-    hipLaunchKernelGGL(topk_classify_kernel, dim3(ggrid), dim3(SB), 0, ctx->stream, off, G, sw.small_max, sw.split_min, k, (int)sizeof(U) * 8, tile_first, glist, sst, ctl);
+    hipLaunchKernelGGL(topk_classify_kernel, dim3(p.ggrid), dim3(SB), 0, ctx->stream, in.off, in.G, sw.small_max, sw.split_min, k, (int)sizeof(U) * 8, p.tile_first, p.glist, p.sst, ctl);
     aqg_kernel_timer_begin(ctx);
-    if (do_small) {
-        hipLaunchKernelGGL((topk_small_kernel<U, KIND>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, off, G, tile_first, sw.small_max, k, vals, pos_out);
-    }
-    if (do_group) {
-        const uint32_t cap = (uint32_t)ctx->num_cu * 8;
-        hipLaunchKernelGGL((topk_group_kernel<U, KIND>), dim3(glcap < cap ? glcap : cap), dim3(SB), 0, ctx->stream, x, off, glist, ctl, k, vals, pos_out);
-    }
-    if (do_split) {
-        const uint64_t chunks = (uint64_t)aqg_ceil_div(n, SPLIT_CHUNK) + scap;
-        const unsigned hgrid = (unsigned)(chunks < (uint64_t)ctx->num_cu * 8 ? chunks : (uint64_t)ctx->num_cu * 8);
-        const unsigned cgrid = scap < 1024u ? scap : 1024u;
-        hipLaunchKernelGGL(select_split_plan_kernel, dim3(1), dim3(SB), 0, ctx->stream, sst, ctl);
-        for (size_t p = 0; p < sizeof(U); ++p) {
-            hipLaunchKernelGGL((select_split_hist_kernel<U, KIND>), dim3(hgrid), dim3(SB), 0, ctx->stream, x, sst, ctl, ghist);
-            hipLaunchKernelGGL((topk_split_choose_kernel<U>), dim3(cgrid), dim3(SB), 0, ctx->stream, sst, ctl, ghist);
+    if (p.do_small) hipLaunchKernelGGL((topk_small_kernel<U, KIND>), dim3(p.ntiles), dim3(SB), 0, ctx->stream, x, in.n, in.off, in.G, p.tile_first, sw.small_max, k, vals, pos_out);
+    if (p.do_group) hipLaunchKernelGGL((topk_group_kernel<U, KIND>), dim3(p.wgrid), dim3(SB), 0, ctx->stream, x, in.off, p.glist, ctl, k, vals, pos_out);
+    if (p.do_split) {
+        hipLaunchKernelGGL(select_split_plan_kernel, dim3(1), dim3(SB), 0, ctx->stream, p.sst, ctl);
+        for (size_t d = 0; d < sizeof(U); ++d) {
+            hipLaunchKernelGGL((select_split_hist_kernel<U, KIND>), dim3(p.hgrid), dim3(SB), 0, ctx->stream, x, p.sst, ctl, p.ghist);
+            hipLaunchKernelGGL((topk_split_choose_kernel<U>), dim3(p.cgrid), dim3(SB), 0, ctx->stream, p.sst, ctl, p.ghist);
         }
-        hipLaunchKernelGGL((topk_split_collect_kernel<U, KIND>), dim3(hgrid), dim3(SB), 0, ctx->stream, x, sst, ctl, k, cur, cand);
-        hipLaunchKernelGGL((topk_split_emit_kernel<U, KIND>), dim3(cgrid), dim3(SB), 0, ctx->stream, x, sst, ctl, k, cand, vals, pos_out);
+        hipLaunchKernelGGL((topk_split_collect_kernel<U, KIND>), dim3(p.hgrid), dim3(SB), 0, ctx->stream, x, p.sst, ctl, k, cur, cand);
+        hipLaunchKernelGGL((topk_split_emit_kernel<U, KIND>), dim3(p.cgrid), dim3(SB), 0, ctx->stream, x, p.sst, ctl, k, cand, vals, pos_out);
     }
     aqg_kernel_timer_end(ctx);
     return aqg_check_launch(ctx, "top-k selection");
 }
 template <class U, int KIND>
-int run_topk_order(aqg_ctx* ctx, int order, const void* x, uint32_t n, const uint32_t* off, uint32_t G, uint32_t k, SelSwitches sw, void* vals, uint32_t* pos_out) {
-    if (order == AQG_ORDER_DESC) return run_topk<U, KIND | KIND_DESC>(ctx, x, n, off, G, k, sw, vals, pos_out);
-    return run_topk<U, KIND>(ctx, x, n, off, G, k, sw, vals, pos_out);
+int run_topk_order(aqg_ctx* ctx, int order, const SelInput& in, uint32_t k, SelSwitches sw, void* vals, uint32_t* pos_out) {
+    if (order == AQG_ORDER_DESC) return run_topk<U, KIND | KIND_DESC>(ctx, in, k, sw, vals, pos_out);
+    return run_topk<U, KIND>(ctx, in, k, sw, vals, pos_out);
 }
-int dispatch_topk(aqg_ctx* ctx, int order, int t, const void* x, uint32_t n, const uint32_t* off, uint32_t G, uint32_t k, SelSwitches sw, void* vals, uint32_t* pos_out) {
-    switch (t) {
-    case AQG_UINT8: case AQG_BOOL: return run_topk_order<uint8_t, KIND_UNSIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_UINT16: return run_topk_order<uint16_t, KIND_UNSIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_UINT32: return run_topk_order<uint32_t, KIND_UNSIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_UINT64: return run_topk_order<uint64_t, KIND_UNSIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_INT8: return run_topk_order<uint8_t, KIND_SIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_INT16: return run_topk_order<uint16_t, KIND_SIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_INT32: return run_topk_order<uint32_t, KIND_SIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_INT64: return run_topk_order<uint64_t, KIND_SIGNED>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_FLOAT: return run_topk_order<uint32_t, KIND_FP>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    case AQG_DOUBLE: return run_topk_order<uint64_t, KIND_FP>(ctx, order, x, n, off, G, k, sw, vals, pos_out);
-    }
-    return AQG_ERR_DTYPE;
+int dispatch_topk(aqg_ctx* ctx, int order, int t, const SelInput& in, uint32_t k, SelSwitches sw, void* vals, uint32_t* pos_out) {
+    return dispatch_kind(t, [&]<class U, int KIND>() { return run_topk_order<U, KIND>(ctx, order, in, k, sw, vals, pos_out); });
 }
 int check_args(aqg_ctx* ctx, int order, int t, uint32_t k) {
     if (order != AQG_ORDER_ASC && order != AQG_ORDER_DESC) return aqg_fail(ctx, AQG_ERR_ARG, "top-k: order must be AQG_ORDER_ASC or AQG_ORDER_DESC");
@@ -447,6 +269,15 @@ int check_grouped(aqg_ctx* ctx, const aqg_groupby* g, int order, int t, const vo
     return AQG_OK;
 }
 
+int grouped_topk(aqg_ctx* ctx, aqg_groupby* g, int order, int t, const void* x, bool row_layout, uint32_t k, void* vals, uint32_t* pos_out) {
+    AQG_TRY(check_grouped(ctx, g, order, t, x, k, vals));
+    const SelSwitches sw = select_switches();
+    SelInput in;
+    AQG_TRY(select_prologue(ctx, g, x, g->n, esz_of(t), topk_ws_bytes(g->n, g->ngroups, k, sw), row_layout, &in));
+    if (!in.G) return AQG_OK;
+    return dispatch_topk(ctx, order, t, in, k, sw, vals, pos_out);
+}
+
 } // namespace
 
 extern "C" {
@@ -456,48 +287,23 @@ int aqg_topk(aqg_ctx* ctx, int order, int t, const void* x, uint32_t n, uint32_t
     AQG_TRY(check_args(ctx, order, t, k));
     if (!x && n) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_topk: null column");
     AQG_CHECK_ROWS(ctx, n, "aqg_topk");
-    AQG_TRY(ensure_ctl(ctx));
-    if (n == 0) {                                           // no row: k empty slots
+    const SelSwitches sw = select_switches();
+    SelInput in;
+    AQG_TRY(select_prologue(ctx, nullptr, x, n, esz_of(t), topk_ws_bytes(n, 1, k, sw), false, &in));
+    if (!in.G) {                                            // no row: k empty slots
         AQG_HIP(ctx, hipMemsetAsync(vals_out_dev, 0, (size_t)k * esz_of(t), ctx->stream));
         if (rows_out_dev) AQG_HIP(ctx, hipMemsetAsync(rows_out_dev, 0xFF, (size_t)k * 4, ctx->stream));
         return AQG_OK;
     }
-    const SelSwitches sw = select_switches();
-    AQG_TRY(aqg_ws_reset(ctx));
-    AQG_TRY(aqg_ws_ensure(ctx, topk_ws_bytes(n, 1, k, sw)));
-    uint32_t* ctl = ctx->select_ctl;
-    hipLaunchKernelGGL(flat_offsets_kernel, dim3(1), dim3(1), 0, ctx->stream, ctl + CTL_OFF, n);
-    return dispatch_topk(ctx, order, t, x, n, ctl + CTL_OFF, 1, k, sw, vals_out_dev, rows_out_dev);
+    return dispatch_topk(ctx, order, t, in, k, sw, vals_out_dev, rows_out_dev);
 }
 
 int aqg_grouped_topk_flat(aqg_ctx* ctx, aqg_groupby* g, int order, int t, const void* xflat, uint32_t k, void* vals_out_dev, uint32_t* pos_out_dev) {
-    AQG_TRY(check_grouped(ctx, g, order, t, xflat, k, vals_out_dev));
-    AQG_TRY(ensure_ctl(ctx));
-    const uint32_t n = g->n, G = g->ngroups;
-    if (n == 0 || G == 0) return AQG_OK;
-    const uint32_t* off = aqg_groupby_offsets(g);
-    if (!off) return AQG_ERR_HIP;
-    const SelSwitches sw = select_switches();
-    AQG_TRY(aqg_ws_reset(ctx));
-    AQG_TRY(aqg_ws_ensure(ctx, topk_ws_bytes(n, G, k, sw)));
-    return dispatch_topk(ctx, order, t, xflat, n, off, G, k, sw, vals_out_dev, pos_out_dev);
+    return grouped_topk(ctx, g, order, t, xflat, /*row_layout=*/false, k, vals_out_dev, pos_out_dev);
 }
 
 int aqg_grouped_topk(aqg_ctx* ctx, aqg_groupby* g, int order, int t, const void* x, uint32_t k, void* vals_out_dev, uint32_t* pos_out_dev) {
-    AQG_TRY(check_grouped(ctx, g, order, t, x, k, vals_out_dev));
-    AQG_TRY(ensure_ctl(ctx));
-    const uint32_t n = g->n, G = g->ngroups;
-    if (n == 0 || G == 0) return AQG_OK;
-    const uint32_t* off = aqg_groupby_offsets(g);
-    if (!off) return AQG_ERR_HIP;
-    const SelSwitches sw = select_switches();
-    const int esz = esz_of(t);
-    AQG_TRY(aqg_ws_reset(ctx));
-    AQG_TRY(aqg_ws_ensure(ctx, (size_t)n * esz + 4096 + aqg_postproc_ws_bytes(n, G, esz) + topk_ws_bytes(n, G, k, sw)));
-    unsigned char* xs;
-    AQG_TRY(aqg_ws_get(ctx, (size_t)n * esz + 64, &xs));
-    AQG_TRY(aqg_radix_by_group(ctx, g, nullptr, x, esz, xs, /*ws_managed=*/true));
-    return dispatch_topk(ctx, order, t, xs, n, off, G, k, sw, vals_out_dev, pos_out_dev);
+    return grouped_topk(ctx, g, order, t, x, /*row_layout=*/true, k, vals_out_dev, pos_out_dev);
 }
 
 } // extern "C"

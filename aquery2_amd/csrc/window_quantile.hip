@@ -13,30 +13,28 @@
 // copies it into LDS and keeps the ranks of the full window in registers.
 // Both layouts are one kernel (scan_window.hpp's whole_column / by_group): by_group holds the length of every output's window in LDS
 // (by_group::len, the rule of sumw / minw), whole_column computes it and loads nothing for groups.
-#include "groupby_handle.hpp"
 #include "scan_window.hpp"
-#include "select_radix.hpp"
+#include "select_host.hpp"
 
 namespace {
 using aqgscan::by_group;
 using aqgscan::whole_column;
 using selradix::image_is_shared;
 using selradix::image_of;
+using selradix::QArgs;
+using selradix::QMAX;
 using selradix::value_of;
 
 constexpr int WQ_SB = 256;                        // lanes per workgroup
 constexpr uint32_t WQ_TILE = 2048;                // outputs per workgroup: the halo of the longest window is a third of the rows it holds
-constexpr uint32_t QMAX = AQG_QUANTILES_MAX;
 constexpr uint32_t NO_RANK = 0xFFFFFFFFu;
 static_assert(AQG_WINQ_MAX_W <= 0xFFFF, "16-bit ranks and window lengths");
 
 // LDS bytes of the images of a tile and its halo (whole 16 bytes: the 16-bit arrays follow)
 __host__ __device__ constexpr size_t img_bytes(size_t esz, uint32_t w) { return (((size_t)w - 1 + WQ_TILE) * esz + 15) & ~(size_t)15; }
 
-struct WQArgs { uint32_t nq, den, which, num[QMAX]; };
-
 // R[(len - 1) * nq + j] = rank of quantile j in a window of len rows, 1 <= len <= w
-__global__ void __launch_bounds__(WQ_SB) winq_ranks_kernel(WQArgs qa, uint32_t w, uint16_t* __restrict__ R) {
+__global__ void __launch_bounds__(WQ_SB) winq_ranks_kernel(QArgs qa, uint32_t w, uint16_t* __restrict__ R) {
     const uint32_t k = blockIdx.x * WQ_SB + threadIdx.x;
     if (k >= w * qa.nq) return;
     const uint64_t p = (uint64_t)qa.num[k % qa.nq] * (k / qa.nq);
@@ -103,7 +101,7 @@ size_t winq_lds_bytes(size_t esz, uint32_t w, uint32_t nq, bool seg) { return im
 size_t winq_ws_bytes(uint32_t w, uint32_t nq) { return (size_t)w * nq * 2 + 4096; }
 
 template <class U, int KIND, class M>
-int run_winq(aqg_ctx* ctx, const WQArgs& qa, const void* x, uint32_t n, uint32_t w, M seg, void* out) {
+int run_winq(aqg_ctx* ctx, const QArgs& qa, const void* x, uint32_t n, uint32_t w, M seg, void* out) {
     uint16_t* R;
     AQG_TRY(aqg_ws_get(ctx, (size_t)w * qa.nq, &R));
     hipLaunchKernelGGL(winq_ranks_kernel, dim3(aqg_ceil_div(w * qa.nq, WQ_SB)), dim3(WQ_SB), 0, ctx->stream, qa, w, R);
@@ -111,33 +109,13 @@ int run_winq(aqg_ctx* ctx, const WQArgs& qa, const void* x, uint32_t n, uint32_t
                                   static_cast<const U*>(x), n, w, seg, qa.nq, (const uint16_t*)R, static_cast<U*>(out));
 }
 template <class M>
-int dispatch_winq(aqg_ctx* ctx, const WQArgs& qa, int t, const void* x, uint32_t n, uint32_t w, M seg, void* out) {
-    using namespace selradix;
-    switch (t) {
-    case AQG_UINT8: case AQG_BOOL: return run_winq<uint8_t, KIND_UNSIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_UINT16: return run_winq<uint16_t, KIND_UNSIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_UINT32: return run_winq<uint32_t, KIND_UNSIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_UINT64: return run_winq<uint64_t, KIND_UNSIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_INT8: return run_winq<uint8_t, KIND_SIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_INT16: return run_winq<uint16_t, KIND_SIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_INT32: return run_winq<uint32_t, KIND_SIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_INT64: return run_winq<uint64_t, KIND_SIGNED>(ctx, qa, x, n, w, seg, out);
-    case AQG_FLOAT: return run_winq<uint32_t, KIND_FP>(ctx, qa, x, n, w, seg, out);
-    case AQG_DOUBLE: return run_winq<uint64_t, KIND_FP>(ctx, qa, x, n, w, seg, out);
-    }
-    return AQG_ERR_DTYPE;
+int dispatch_winq(aqg_ctx* ctx, const QArgs& qa, int t, const void* x, uint32_t n, uint32_t w, M seg, void* out) {
+    return selradix::dispatch_kind(t, [&]<class U, int KIND>() { return run_winq<U, KIND>(ctx, qa, x, n, w, seg, out); });
 }
 
 // the checks every entry shares; fills qa and the effective window *ww = min(w, n)
-int check_winq(aqg_ctx* ctx, int which, uint32_t nq, const uint32_t* num, uint32_t den, int t, const void* x, uint32_t n, uint32_t w, const void* out, WQArgs* qa, uint32_t* ww) {
-    if (which != AQG_SEL_LOWER && which != AQG_SEL_UPPER) return aqg_fail(ctx, AQG_ERR_ARG, "window quantiles: which must be AQG_SEL_LOWER or AQG_SEL_UPPER");
-    if (nq < 1 || nq > QMAX || !num || den < 1) return aqg_fail(ctx, AQG_ERR_ARG, "window quantiles: 1 <= nq <= AQG_QUANTILES_MAX ranks num[j] / den with den >= 1");
-    *qa = WQArgs{};
-    qa->nq = nq; qa->den = den; qa->which = (uint32_t)which;
-    for (uint32_t j = 0; j < nq; ++j) {
-        if (num[j] > den) return aqg_fail(ctx, AQG_ERR_ARG, "window quantiles: num[j] > den");
-        qa->num[j] = num[j];
-    }
+int check_winq(aqg_ctx* ctx, int which, uint32_t nq, const uint32_t* num, uint32_t den, int t, const void* x, uint32_t n, uint32_t w, const void* out, QArgs* qa, uint32_t* ww) {
+    AQG_TRY(selradix::check_quant(ctx, "window quantiles", which, nq, num, den, qa));
     if (w < 1) return aqg_fail(ctx, AQG_ERR_ARG, "window quantiles: w >= 1");
     const int esz = seldev::esz_of(t);
     if (!esz) return aqg_fail(ctx, AQG_ERR_DTYPE, "window quantiles: 1-, 2-, 4- and 8-byte numeric columns and BOOL");
@@ -163,7 +141,7 @@ extern "C" {
 
 int aqg_window_quantiles(aqg_ctx* ctx, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* x, uint32_t n, uint32_t w, void* out_dev) {
     if (!ctx) return AQG_ERR_ARG;
-    WQArgs qa;
+    QArgs qa;
     uint32_t ww;
     AQG_TRY(check_winq(ctx, which, nq, num_host, den, t, x, n, w, out_dev, &qa, &ww));
     if (n == 0) return AQG_OK;
@@ -174,7 +152,7 @@ int aqg_window_quantiles(aqg_ctx* ctx, int which, uint32_t nq, const uint32_t* n
 
 int aqg_grouped_window_quantiles_flat(aqg_ctx* ctx, aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* xflat, uint32_t w, void* out_flat_dev) {
     AQG_TRY(check_grouped(ctx, g));
-    WQArgs qa;
+    QArgs qa;
     uint32_t ww;
     AQG_TRY(check_winq(ctx, which, nq, num_host, den, t, xflat, g->n, w, out_flat_dev, &qa, &ww));
     if (g->n == 0 || g->ngroups == 0) return AQG_OK;
@@ -186,7 +164,7 @@ int aqg_grouped_window_quantiles_flat(aqg_ctx* ctx, aqg_groupby* g, int which, u
 
 int aqg_grouped_window_quantiles(aqg_ctx* ctx, aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* x, uint32_t w, void* out_flat_dev) {
     AQG_TRY(check_grouped(ctx, g));
-    WQArgs qa;
+    QArgs qa;
     uint32_t ww;
     AQG_TRY(check_winq(ctx, which, nq, num_host, den, t, x, g->n, w, out_flat_dev, &qa, &ww));
     const uint32_t n = g->n;
