@@ -58,6 +58,15 @@ WINQ_PROTOTYPES = {
     "aqg_grouped_window_quantiles_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
     "aqg_window_quantiles_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
 }
+# ctypes prototypes of the exponential moving averages (applied by load_library)
+EMA_RECURSIVE, EMA_ADJUSTED = 0, 1
+EMA_PROTOTYPES = {
+    "aqg_scan_ema": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p],
+    "aqg_grouped_ema": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    "aqg_grouped_ema_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    "aqg_decay_from_times": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p],
+    "aqg_grouped_decay_from_times_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p],
+}
 # ctypes prototypes of the count-distinct entries (applied by load_library)
 DISTINCT_PROTOTYPES = {
     "aqg_count_distinct": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)],
@@ -124,7 +133,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -740,6 +749,37 @@ class Device:
         t, h = C.c_uint32(), C.c_uint32()
         self._chk(self.lib.aqg_window_quantiles_last(self.ctx, C.byref(t), C.byref(h)), "aqg_window_quantiles_last")
         return t.value, h.value
+
+    # -- exponential moving averages (ordered scan of affine maps: include/aqg.h, exponential moving averages section)
+    def ema(self, x, alpha=None, decay=None, mode=EMA_RECURSIVE, keep=False, out=None):
+        """y[i] = b_i x[i] + a_i y[i-1] (EMA_RECURSIVE) or its bias-corrected form N[i] / D[i] (EMA_ADJUSTED) over the whole column:
+        a constant `alpha` (a_i = 1 - alpha), or a `decay` column of doubles (a_i = decay[i]); n doubles"""
+        xd = self._dev(x)
+        dd = self._dev(np.asarray(decay, np.float64) if not isinstance(decay, DevBuf) else decay) if decay is not None else None
+        out = out if out is not None else self.empty(xd.n, np.float64)
+        self._chk(self.lib.aqg_scan_ema(self.ctx, mode, xd.tag, xd.ptr, xd.n, 0.0 if alpha is None else float(alpha), dd.ptr if dd else None, out.ptr), "aqg_scan_ema")
+        return out if keep else out.to_host()
+
+    def grouped_ema(self, gb, x, alpha=None, decay=None, mode=EMA_RECURSIVE, flat=False, keep=False, out=None):
+        """ema within every group of a build, n doubles in the flat layout: `x` (and `decay`) in row layout, or (flat=True) already
+        in the flat layout"""
+        xd = self._dev(x)
+        dd = self._dev(np.asarray(decay, np.float64) if not isinstance(decay, DevBuf) else decay) if decay is not None else None
+        out = out if out is not None else self.empty(xd.n, np.float64)
+        fn = self.lib.aqg_grouped_ema_flat if flat else self.lib.aqg_grouped_ema
+        self._chk(fn(self.ctx, gb.h, mode, xd.tag, xd.ptr, 0.0 if alpha is None else float(alpha), dd.ptr if dd else None, out.ptr), "aqg_grouped_ema")
+        return out if keep else out.to_host()
+
+    def decay_from_times(self, t, halflife, gb=None, keep=False, out=None):
+        """decay[i] = 2^(-|t[i] - t[i-1]| / halflife), decay[0] = 1: the decay column of a time-decayed ema (numeric times, or a
+        key_col of DATE / TIME); gb: `t` is in the flat layout of that build, and every group's first decay is 1"""
+        td = self._dev(t)
+        out = out if out is not None else self.empty(td.n, np.float64)
+        if gb is not None:
+            self._chk(self.lib.aqg_grouped_decay_from_times_flat(self.ctx, gb.h, td.tag, td.ptr, float(halflife), out.ptr), "aqg_grouped_decay_from_times_flat")
+        else:
+            self._chk(self.lib.aqg_decay_from_times(self.ctx, td.tag, td.ptr, td.n, float(halflife), out.ptr), "aqg_decay_from_times")
+        return out if keep else out.to_host()
 
     # -- count distinct (include/aqg.h, count distinct section)
     def count_distinct(self, x):

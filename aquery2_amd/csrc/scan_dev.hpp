@@ -98,6 +98,28 @@ template <class T> struct max_alg {
     __device__ static A op(A a, A b) { return b > a ? b : a; }
 };
 template <class T, bool IS_MAX> using minmax_alg = std::conditional_t<IS_MAX, max_alg<T>, min_alg<T>>;
+// affine maps y -> a y + b of the exponential moving averages (ema.hip): a row lifts to {decay, weight * x} (recursive form) or to
+// {decay, x, 1} (adjusted form: numerator and denominator ride the same decay), and op(l, r) is "l, then r".  THE MAPS DO NOT COMMUTE:
+// only the ordered parts of the skeleton may fold them -- the lane's serial loop, block_scan_excl, launch_agg_scan, seg_alg -- never
+// block_fold or the chained look-back of scan.hip.  A slice's first row lifts to a map with a = 0, which discards what precedes it.
+// fma: one rounding per component and combine (the build contracts nothing by itself).
+struct ema_rec { double a, b; };
+struct ema_adj { double a, num, den; };
+template <bool ADJ> struct ema_alg {
+    using A = std::conditional_t<ADJ, ema_adj, ema_rec>;
+    __device__ static A identity() { if constexpr (ADJ) return {1.0, 0.0, 0.0}; else return {1.0, 0.0}; }
+    // decay outside [0, 1] (NaN included) poisons the slice like a NaN row: a NaN factor makes every later combine NaN
+    __device__ static A lift(double decay, double weight, double x) {
+        if (!(decay >= 0.0 && decay <= 1.0)) decay = weight = __builtin_nan("");
+        if constexpr (ADJ) return {decay, decay != decay ? decay : x, 1.0}; else return {decay, weight * x};
+    }
+    __device__ static A lift_first(double x) { if constexpr (ADJ) return {0.0, x, 1.0}; else return {0.0, x}; }
+    __device__ static A op(A l, A r) {
+        if constexpr (ADJ) return {l.a * r.a, fma(r.a, l.num, r.num), fma(r.a, l.den, r.den)};
+        else return {l.a * r.a, fma(r.a, l.b, r.b)};
+    }
+    __device__ static double value(A m) { if constexpr (ADJ) return m.num / m.den; else return m.b; }
+};
 
 // exclusive scan of one value per lane across the workgroup; `total` = fold of all lanes
 template <class ALG, class A> __device__ inline A block_scan_excl(A v, A* lds_w /* >= 5 */, A& total) {

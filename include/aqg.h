@@ -334,6 +334,44 @@ int aqg_grouped_window_quantiles(aqg_ctx* ctx, struct aqg_groupby* g, int which,
 int aqg_grouped_window_quantiles_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* xflat, uint32_t w, void* out_flat_dev);
 int aqg_window_quantiles_last(aqg_ctx* ctx, uint32_t* tile_rows, uint32_t* halo_rows);
 
+/* ---- exponential moving averages ------------------------------------------------
+ * The decayed averages beside avgs / avgw: kdb's `ema`, pandas' `ewm(...).mean()`, "decayed price by symbol".  THE REFERENCE HAS NO SUCH
+ * FUNCTION (server/aggregations.h stops at the windows): these entries stand in for the host loop per group a user would otherwise
+ * write, and their contract is this comment, held by the exact model tests/ema_model.py.
+ * Rows are taken in the order of the layout scanned: the column's own order, or the order of vecs[g] (the flat layout of a build,
+ * descending row ids, like every grouped scan).  x is converted to double by round-to-nearest (exact but for 64-bit integers); results
+ * are doubles; i counts from the first row of the SLICE (the column, or the row's group), which has no predecessor.
+ *   AQG_EMA_RECURSIVE   y[0] = x[0], y[i] = b_i x[i] + a_i y[i-1]                                     (kdb ema, pandas adjust=False)
+ *   AQG_EMA_ADJUSTED    N[0] = x[0], D[0] = 1, N[i] = a_i N[i-1] + x[i], D[i] = a_i D[i-1] + 1, y[i] = N[i] / D[i]     (pandas adjust=True)
+ * Decay: a constant alpha, 0 < alpha <= 1 (anything else, NaN included: AQG_ERR_ARG) -- a_i = fl(1 - alpha), b_i = alpha -- or, when
+ * `decay` is not NULL (alpha is then ignored), a device column of n doubles in the layout of x: a_i = decay[i] in [0, 1],
+ * b_i = fl(1 - decay[i]).  The decay of a slice's first row is never read into the result.
+ * Non-finite rows: from the first row of a slice whose x is NaN or +-Inf, or whose decay is NaN or outside [0, 1], to the slice's end
+ * every output is non-finite (WHICH non-finite value is unspecified); rows before it and every other group are unaffected.  There is no
+ * NULL-skipping -- pandas' ignore_na has no counterpart here, because the reference has no nulls.
+ * The maps are composed in a tree order fixed by n, the group starts and the tile geometry: results are bit-reproducible from call to
+ * call and within 4 (i + 2) 2^-53 max|x| (RECURSIVE) / 9 (i + 2) 2^-53 max|x| (ADJUSTED) of the exact value (max over the slice's rows
+ * up to i); the flat and the grouped call need not agree bit for bit.
+ *   aqg_scan_ema          the whole column
+ *   aqg_grouped_ema       every group's rows, x (and decay) in ROW layout (brought into the flat layout in workspace, like aqg_grouped_scan)
+ *   aqg_grouped_ema_flat  the same over columns already in the FLAT LAYOUT of the build; out in the flat layout either way
+ * Dtypes: those of aqg_scan (every numeric type); 128-bit and non-numeric types: AQG_ERR_DTYPE.  A bad mode, a handle not made by
+ * aqg_groupby_build, a NULL column with rows, `out` overlapping an input: AQG_ERR_ARG.  Every error returns with nothing written;
+ * n == 0 or G == 0: AQG_OK.  Asynchronous on the context's stream, scratch from the context workspace, three to five launches whatever
+ * n and G are (the row-layout form adds the flattens).
+ * aqg_decay_from_times: decay[i] = 2^(-|t[i] - t[i-1]| / halflife), decay[0] = 1 -- a time-decayed average without a host pass (pandas
+ * ewm(halflife=h, times=t)).  The absolute difference serves ascending columns and the descending order of vecs[g] alike, and group
+ * borders need no care because a group's first decay is not read.  t: numeric (64-bit integers subtract in integer arithmetic before
+ * the conversion), AQG_DATE (differences in days) or AQG_TIME (in milliseconds); anything else AQG_ERR_DTYPE.  halflife > 0 and
+ * finite, in the unit of the differences, else AQG_ERR_ARG.  One element-wise launch.  aqg_grouped_decay_from_times_flat is the same over
+ * a column in the flat layout of a build with decay = 1 at every group's first row (what the header layer hands out as a group's slice). */
+enum { AQG_EMA_RECURSIVE = 0, AQG_EMA_ADJUSTED = 1 };
+int aqg_scan_ema(aqg_ctx* ctx, int mode, int t, const void* x, uint32_t n, double alpha, const double* decay_dev /* NULL: constant alpha */, double* out);
+int aqg_grouped_ema(aqg_ctx* ctx, struct aqg_groupby* g, int mode, int t, const void* x /* row layout */, double alpha, const double* decay_row /* row layout or NULL */, double* out_flat);
+int aqg_grouped_ema_flat(aqg_ctx* ctx, struct aqg_groupby* g, int mode, int t, const void* xflat, double alpha, const double* decay_flat, double* out_flat);
+int aqg_decay_from_times(aqg_ctx* ctx, int t, const void* times, uint32_t n, double halflife, double* decay_out);
+int aqg_grouped_decay_from_times_flat(aqg_ctx* ctx, struct aqg_groupby* g, int t, const void* times_flat, double halflife, double* decay_flat);
+
 /* ---- count distinct ----------------------------------------------------------
  * `count(distinct x)`: the generator emits `(x).distinct_size()` (common/types.py:271-277), under GROUP BY `(x[val]).distinct_size()`
  * inside the generated loop (engine/ast.py:749-784).  Replaces vector_type::distinct_size (server/vector_type.hpp:153-174) and

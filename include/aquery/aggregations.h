@@ -102,6 +102,59 @@ template <class T, template <typename...> class VT> inline void device_quantiles
         dev::check(aqg_quantiles(rt.ctx(), which, m, nums + b, den, dev::tag_of<T>::value, in.d, arr.size, out + b), "aqg_quantiles");
     }
 }
+// ret = ema / ewma of arr (include/aqg.h, exponential moving averages section): mode AQG_EMA_RECURSIVE / AQG_EMA_ADJUSTED, a constant alpha
+// (dec == nullptr) or a decay column `dec` of arr.size doubles.  A per-group temporary of the generated loop that is ALL of its group is
+// answered for all groups by one aqg_grouped_ema_flat (Runtime::vcol_ema) and `ret` becomes this group's slice of that result; the decay
+// form takes that path only when the decay column is such a temporary of the SAME group.  Any other vector -- a view shorter than its
+// group (`subvec` shares the temporary's address) among them -- goes through aqg_scan_ema on its own rows.
+template <class T, template <typename...> class VT, class Ret> inline void device_ema(int mode, double alpha, const double* dec, bool dec_borrowed, const VT<T>& arr, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    static_assert(std::is_same_v<RT, double>, "ema / ewma: the result holds doubles");
+    auto& rt = dev::Runtime::get();
+    const uint32_t n = arr.size;
+    if (n == 0) return;
+    if (rt.deferred_whole(arr.container, n)) {
+        dev::Entry* e = rt.deferred_at(arr.container);
+        dev::Entry* ed = dec ? (rt.deferred_whole(dec, n) ? rt.deferred_at(dec) : nullptr) : nullptr;
+        if (!dec || (ed && ed->dgroup == e->dgroup && ed->dg == e->dg && ed->dgroup->vcols[ed->dv].tag == AQG_DOUBLE)) {
+            dev::GroupCtx* gc = e->dgroup;
+            const uint32_t g = e->dg;
+            const int r = rt.vcol_ema(gc, e->dv, mode, alpha, ed ? ed->dv : -1);
+            rt.defer_slice(ret.container, (size_t)n * sizeof(RT), gc, g, r);
+            if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+            return;
+        }
+    }
+    void* dout = rt.result(ret.container, (size_t)n * sizeof(RT));
+    dev::In in(arr.container, (size_t)n * sizeof(T), arr.capacity == 0);
+    if (dec) {
+        dev::In ind(dec, (size_t)n * sizeof(double), dec_borrowed);
+        dev::check(aqg_scan_ema(rt.ctx(), mode, dev::tag_of<std::remove_cv_t<T>>::value, in.d, n, alpha, static_cast<const double*>(ind.d), static_cast<double*>(dout)), "aqg_scan_ema");
+    } else dev::check(aqg_scan_ema(rt.ctx(), mode, dev::tag_of<std::remove_cv_t<T>>::value, in.d, n, alpha, nullptr, static_cast<double*>(dout)), "aqg_scan_ema");
+    if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+}
+// ret = decay(halflife, t): 2^(-|t[i] - t[i-1]| / halflife), 1 at the first element; a per-group temporary that is all of its group: one
+// aqg_grouped_decay_from_times_flat for all groups (Runtime::vcol_decay)
+template <class T, template <typename...> class VT, class Ret> inline void device_decay(double halflife, const VT<T>& t, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    static_assert(std::is_same_v<RT, double>, "decay: the result holds doubles");
+    auto& rt = dev::Runtime::get();
+    const uint32_t n = t.size;
+    if (n == 0) return;
+    if (rt.deferred_whole(t.container, n)) {
+        dev::Entry* e = rt.deferred_at(t.container);
+        dev::GroupCtx* gc = e->dgroup;
+        const uint32_t g = e->dg;
+        const int r = rt.vcol_decay(gc, e->dv, halflife);
+        rt.defer_slice(ret.container, (size_t)n * sizeof(RT), gc, g, r);
+        if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+        return;
+    }
+    void* dout = rt.result(ret.container, (size_t)n * sizeof(RT));
+    dev::In in(t.container, (size_t)n * sizeof(T), t.capacity == 0);
+    dev::check(aqg_decay_from_times(rt.ctx(), dev::tag_of<std::remove_cv_t<T>>::value, in.d, n, halflife, static_cast<double*>(dout)), "aqg_decay_from_times");
+    if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+}
 // ret[i] = the row of rank floor (AQG_SEL_LOWER) / ceil (AQG_SEL_UPPER) of num (len - 1) / den of the last len = min(w, i + 1) elements of
 // arr in ascending order (include/aqg.h, moving quantiles section).  A per-group temporary of the generated loop is answered for ALL groups
 // by one aqg_grouped_window_quantiles_flat (Runtime::vcol_window_quantile) and `ret` becomes this group's slice of that result, exactly as
@@ -314,6 +367,41 @@ template <class T, template <typename...> class VT, class Ret, std::enable_if_t<
 void medianw(uint32_t w, const VT<T>& arr, Ret& ret) { aq::device_window_quantile(AQG_SEL_LOWER, w, 1, 2, arr, ret); }
 template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
 inline decayed_t<VT, T> medianw(uint32_t w, const VT<T>& arr) { decayed_t<VT, T> ret(arr.size); aq::device_window_quantile(AQG_SEL_LOWER, w, 1, 2, arr, ret); return ret; }
+
+// ema(alpha, v) / ewma(alpha, v): the exponential moving average y[i] = alpha v[i] + (1 - alpha) y[i-1], y[0] = v[0] (kdb's ema, pandas'
+// ewm(adjust=False)) and its bias-corrected form (pandas' default, adjust=True); emad(decay, v) / ewmad(decay, v) take a decay COLUMN in
+// place of 1 - alpha, and decay(halflife, t) = decayt(halflife, t) makes one from a time column: 2^(-|t[i] - t[i-1]| / halflife).  Doubles; the reference's header
+// has none of them (include/aqg.h, exponential moving averages section).  Integer alphas and halflives convert.
+#define AQ_EMA(name, mode)                                                                                        \
+    template <class A, class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T> && std::is_arithmetic_v<A>>* = nullptr> \
+    void name(A alpha, const VT<T>& arr, Ret& ret) { aq::device_ema(mode, (double)alpha, nullptr, false, arr, ret); }   \
+    template <class A, class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T> && std::is_arithmetic_v<A>>* = nullptr> \
+    inline decayed_t<VT, double> name(A alpha, const VT<T>& arr) { decayed_t<VT, double> ret(arr.size); aq::device_ema(mode, (double)alpha, nullptr, false, arr, ret); return ret; } \
+    template <class A, class T, std::enable_if_t<std::is_arithmetic_v<A> && std::is_arithmetic_v<T>>* = nullptr> constexpr T name(A, const T& v) { return v; }
+#define AQ_EMAD(name, mode)                                                                                       \
+    template <template <typename...> class VD, class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T> && aq::is_vt<VD, double>>* = nullptr> \
+    void name(const VD<double>& dec, const VT<T>& arr, Ret& ret) {                                              \
+        if (dec.size != arr.size) aq::dev::check(AQG_ERR_ARG, #name ": the decay column and the values differ in length"); \
+        aq::device_ema(mode, 0.0, dec.container, dec.capacity == 0, arr, ret);                                                       \
+    }                                                                                                             \
+    template <template <typename...> class VD, class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T> && aq::is_vt<VD, double>>* = nullptr> \
+    inline decayed_t<VT, double> name(const VD<double>& dec, const VT<T>& arr) { decayed_t<VT, double> ret(arr.size); name(dec, arr, ret); return ret; }
+AQ_EMA(ema, AQG_EMA_RECURSIVE)
+AQ_EMA(ewma, AQG_EMA_ADJUSTED)
+AQ_EMAD(emad, AQG_EMA_RECURSIVE)
+AQ_EMAD(ewmad, AQG_EMA_ADJUSTED)
+#undef AQ_EMA
+#undef AQ_EMAD
+// (decayt is the name generated code can use: under its `using namespace std` a call to `decay` is ambiguous with std::decay)
+#define AQ_DECAY(name)                                                                                            \
+    template <class H, class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T> && std::is_arithmetic_v<H>>* = nullptr> \
+    void name(H halflife, const VT<T>& t, Ret& ret) { aq::device_decay((double)halflife, t, ret); }              \
+    template <class H, class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T> && std::is_arithmetic_v<H>>* = nullptr> \
+    inline decayed_t<VT, double> name(H halflife, const VT<T>& t) { decayed_t<VT, double> ret(t.size); aq::device_decay((double)halflife, t, ret); return ret; } \
+    template <class H, class T, std::enable_if_t<std::is_arithmetic_v<H> && std::is_arithmetic_v<T>>* = nullptr> constexpr double name(H, const T&) { return 1.0; }
+AQ_DECAY(decay)
+AQ_DECAY(decayt)
+#undef AQ_DECAY
 
 template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
 inline decayed_t<VT, types::GetFPType<T>> ratios(const VT<T>& arr) { return ratiow(1, arr); }

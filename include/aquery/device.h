@@ -258,6 +258,41 @@ public:
         if (rc != AQG_OK) die("aqg_grouped_window_quantiles_flat", rc, ctx_);
         return vcol_new(c, key, r);
     }
+    // ema / ewma of every group's slice (mode: AQG_EMA_RECURSIVE / AQG_EMA_ADJUSTED): ONE aqg_grouped_ema_flat over the flat column, whatever
+    // the number of groups.  vdecay < 0: the constant alpha; else the decay column `vdecay` of the SAME grouping (alpha is then ignored and
+    // left out of the key).
+    size_t grouped_ema_calls = 0;               // aqg_grouped_ema_flat calls made so far (the tests count them)
+    int vcol_ema(GroupCtx* c, int v, int mode, double alpha, int vdecay) {
+        uint64_t abits = 0;
+        if (vdecay < 0) std::memcpy(&abits, &alpha, 8);
+        const std::array<uint64_t, 6> key{5, (uint64_t)mode, (uint64_t)v, abits, (uint64_t)(vdecay + 1), 0};
+        auto it = c->memo.find(key);
+        if (it != c->memo.end()) return it->second;
+        VCol r; r.layout = 1; r.tag = AQG_DOUBLE;
+        const void* xf = vcol_flat_ptr(c, v);
+        const void* df = vdecay < 0 ? nullptr : vcol_flat_ptr(c, vdecay);
+        int rc = aqg_malloc(ctx(), (size_t)c->n * 8 + 16, &r.dptr);
+        if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+        ++grouped_ema_calls;
+        rc = aqg_grouped_ema_flat(ctx_, c->handle, mode, c->vcols[v].tag, xf, alpha, static_cast<const double*>(df), static_cast<double*>(r.dptr));
+        if (rc != AQG_OK) die("aqg_grouped_ema_flat", rc, ctx_);
+        return vcol_new(c, key, r);
+    }
+    // decay(halflife, t) of every group's slice: one aqg_grouped_decay_from_times_flat over the flat column
+    int vcol_decay(GroupCtx* c, int v, double halflife) {
+        uint64_t hbits;
+        std::memcpy(&hbits, &halflife, 8);
+        const std::array<uint64_t, 6> key{6, hbits, (uint64_t)v, 0, 0, 0};
+        auto it = c->memo.find(key);
+        if (it != c->memo.end()) return it->second;
+        VCol r; r.layout = 1; r.tag = AQG_DOUBLE;
+        const void* tf = vcol_flat_ptr(c, v);
+        int rc = aqg_malloc(ctx(), (size_t)c->n * 8 + 16, &r.dptr);
+        if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+        rc = aqg_grouped_decay_from_times_flat(ctx_, c->handle, c->vcols[v].tag, tf, halflife, static_cast<double*>(r.dptr));
+        if (rc != AQG_OK) die("aqg_grouped_decay_from_times_flat", rc, ctx_);
+        return vcol_new(c, key, r);
+    }
     // l OP r of two columns of the grouping: in row order when both are (one pass over the whole columns), else in the flat layout
     int vcol_ewise(GroupCtx* c, int op, int l, int r, int ot) {
         const std::array<uint64_t, 6> key{2, (uint64_t)op, (uint64_t)l, (uint64_t)r, (uint64_t)ot, 0};
