@@ -4,110 +4,47 @@
 // with a constant decay a_i = 1 - alpha or a decay COLUMN a_i = decay[i] (time-decayed averages: aqg_decay_from_times).
 // The reference has no such function; the contract is include/aqg.h's and the exact model tests/ema_model.py.
 //
-// A row is an affine map (ema_alg, scan_dev.hpp) and the scan composes maps IN ROW ORDER: reduce-then-scan over 2048-row tiles like
-// the prefix scans of scan.hip / segscan.hip -- tile aggregate (ema_reduce_kernel) -> launch_agg_scan -> tile scan with carry-in
-// (ema_scan_kernel) -- through the ordered parts of the skeleton only: the lane's serial loop over its 8 rows, block_scan_excl, the
-// aggregate scan, seg_alg for the grouped form.  Affine maps do not commute, so neither block_fold nor the chained single-pass route of
-// scan.hip may carry them.  No atomics, no look-back: the bracketing depends on n, the group starts and the tile geometry alone, and
-// results are bit-reproducible.
-// The kernels are this file's own because no scan kernel reads two input columns (the decay form), and a lift here takes the row's
-// position in its slice (a first row discards what precedes it) besides its value.
+// A row is an affine map (ema_alg, scan_dev.hpp) and the scan composes maps IN ROW ORDER: the reduce-then-scan pass of scan_prefix.hpp
+// (prefix_reduce_kernel -> launch_agg_scan -> prefix_scan_kernel with the W_EMA writer), which goes through the ordered parts only: the
+// lane's serial loop over its 8 rows, block_scan_excl, the aggregate scan, seg_alg for the grouped form.  Affine maps do not commute,
+// so neither block_fold nor the chained single-pass route of scan.hip may carry them.  No atomics, no look-back: the bracketing depends
+// on n, the group starts and the tile geometry alone, and results are bit-reproducible.
+// What is EMA's own is ema_rows below: two input columns (the decay form), and a lift that takes the row's position in its slice (a
+// first row discards what precedes it) besides its value.
 // HBM-bound: sizeof(T) + 8 bytes per row (constant alpha) or sizeof(T) + 16 (decay column), read twice and written once.
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
-#include "scan_dev.hpp"
+#include "scan_prefix.hpp"
 #include "groupby_handle.hpp"
 
 namespace {
 using namespace aqgscan;
 
-template <bool ADJ, bool SEG> struct ema_carry {
+// one lane's 8 consecutive rows for the kernels of scan_prefix.hpp: values, decays (DEC), the start bits of the 8 positions (flat
+// column: row 0 alone starts a slice -- its lift discards what precedes it, so the fold needs no restart there)
+template <class T, bool ADJ, bool DEC, bool SEG_> struct ema_rows : lane_block<SEG_> {
+    using In = T;
     using ALG = ema_alg<ADJ>;
-    using SA = std::conditional_t<SEG, seg_alg<ALG>, ALG>;
-    using C = typename SA::A;
-};
-
-// one lane's 8 consecutive rows: values, decays (DEC), the start bits of the 8 positions (flat column: row 0 alone starts a slice)
-template <class T, bool ADJ, bool DEC, bool SEG> struct ema_rows {
-    using ALG = ema_alg<ADJ>;
-    using A = typename ALG::A;
-    using C = typename ema_carry<ADJ, SEG>::C;
+    static constexpr bool SEG = SEG_;
+    struct args { const T* x; const double* decay; const uint8_t* heads8; double d, alpha; };
     T v[IT];
     double dc[IT];
-    uint32_t cnt, hb, base;
+    bool row0;
     double d, alpha;
-    __device__ void load(const T* __restrict__ x, const double* __restrict__ decay, const uint8_t* __restrict__ heads8, uint32_t n, double d_, double alpha_) {
-        base = blockIdx.x * TS + threadIdx.x * IT;
-        d = d_; alpha = alpha_;
-        load_tile_items(x, n, base, v, cnt);
-        if constexpr (DEC) { uint32_t c2; load_tile_items(decay, n, base, dc, c2); }
-        if constexpr (SEG) hb = cnt ? heads8[base >> 3] : 0u; else hb = base == 0 ? 1u : 0u;
+    __device__ void load(const args& a, uint32_t n) {
+        this->place(n);
+        d = a.d; alpha = a.alpha;
+        row0 = !SEG && this->base == 0;
+        this->fetch(a.x, n, v);
+        if constexpr (DEC) this->fetch(a.decay, n, dc);
+        this->starts(a.heads8);
     }
-    __device__ bool head(int j) const { return (hb >> j) & 1u; }
-    __device__ A lift(int j) const {
+    __device__ typename ALG::A lift(int j) const {
         const double xd = (double)v[j];
-        if (head(j)) return ALG::lift_first(xd);                       // (its decay is not read into the result)
+        if (SEG ? this->head(j) : (row0 && j == 0)) return ALG::lift_first(xd);     // (its decay is not read into the result)
         if constexpr (DEC) return ALG::lift(dc[j], 1.0 - dc[j], xd); else return ALG::lift(d, alpha, xd);
     }
-    // fold of the lane's rows, in order
-    __device__ C fold() const {
-        if constexpr (SEG) {
-            C a = seg_alg<ALG>::identity();
-#pragma unroll
-            for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) {
-                if (head(j)) { a.v = ALG::identity(); a.s = base + j + 1; ++a.c; }
-                a.v = ALG::op(a.v, lift(j));
-            }
-            return a;
-        } else {
-            A a = ALG::identity();
-#pragma unroll
-            for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) a = ALG::op(a, lift(j));
-            return a;
-        }
-    }
 };
-
-// K1: the composed map of each tile (grouped: of the rows behind its last group start, with the start)
-template <class T, bool ADJ, bool DEC, bool SEG>
-__global__ void __launch_bounds__(SB) ema_reduce_kernel(const T* __restrict__ x, const double* __restrict__ decay, const uint8_t* __restrict__ heads8, uint32_t n,
-                                                        double d, double alpha, typename ema_carry<ADJ, SEG>::C* __restrict__ tile_agg) {
-    using SA = typename ema_carry<ADJ, SEG>::SA;
-    using C = typename ema_carry<ADJ, SEG>::C;
-    __shared__ C lds_w[8];
-    ema_rows<T, ADJ, DEC, SEG> r;
-    r.load(x, decay, heads8, n, d, alpha);
-    C total;
-    block_scan_excl<SA>(r.fold(), lds_w, total);
-    if (threadIdx.x == 0) tile_agg[blockIdx.x] = total;
-}
-// K3: the rows of a tile from its carry-in; the writer stores b, or num / den
-template <class T, bool ADJ, bool DEC, bool SEG>
-__global__ void __launch_bounds__(SB) ema_scan_kernel(const T* __restrict__ x, const double* __restrict__ decay, const uint8_t* __restrict__ heads8, uint32_t n,
-                                                      double d, double alpha, const typename ema_carry<ADJ, SEG>::C* __restrict__ tile_prefix, double* __restrict__ out) {
-    using ALG = ema_alg<ADJ>;
-    using SA = typename ema_carry<ADJ, SEG>::SA;
-    using C = typename ema_carry<ADJ, SEG>::C;
-    __shared__ C lds_w[8];
-    extern __shared__ __align__(16) unsigned char stage_raw[];
-    ema_rows<T, ADJ, DEC, SEG> r;
-    r.load(x, decay, heads8, n, d, alpha);
-    C total;
-    const C excl = block_scan_excl<SA>(r.fold(), lds_w, total);
-    const C pre = SA::op(tile_prefix[blockIdx.x], excl);
-    typename ALG::A run;
-    if constexpr (SEG) run = pre.v; else run = pre;
-    double o[IT];
-#pragma unroll
-    for (int j = 0; j < IT; ++j) {
-        if ((uint32_t)j < r.cnt) {
-            if constexpr (SEG) { if (r.head(j)) run = ALG::identity(); }
-            run = ALG::op(run, r.lift(j));
-        }
-        o[j] = ALG::value(run);
-    }
-    store_tile_striped(out, blockIdx.x * TS, o, n, reinterpret_cast<double*>(stage_raw));
-}
 
 // ---- decay[i] = 2^(-|t[i] - t[i-1]| / halflife), decay[0] = 1 --------------------------------------------------------------------------
 // days of a civil date (proleptic Gregorian) / milliseconds of a time of day: what a difference of the reference's date_t / time_t means
@@ -162,21 +99,6 @@ size_t ema_ws_bytes(uint32_t n) {
     const size_t ntiles = aqg_ceil_div(n, TS);
     return (ntiles + ntiles / CH + 2) * sizeof(SegCarry<ema_adj>) + 8192;
 }
-template <class T, bool ADJ, bool DEC, bool SEG>
-int run_ema(aqg_ctx* ctx, const EmaArgs& ea, const T* x, const uint8_t* heads8, uint32_t n, double* out) {
-    using SA = typename ema_carry<ADJ, SEG>::SA;
-    using C = typename ema_carry<ADJ, SEG>::C;
-    const uint32_t ntiles = aqg_ceil_div(n, TS);
-    C *agg, *chunk_tot;
-    AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
-    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles / CH + 2, &chunk_tot));
-    hipLaunchKernelGGL((ema_reduce_kernel<T, ADJ, DEC, SEG>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, ea.decay, heads8, n, ea.d, ea.alpha, agg);
-    launch_agg_scan<SA>(ctx, agg, ntiles, chunk_tot);
-    aqg_kernel_timer_begin(ctx);
-    hipLaunchKernelGGL((ema_scan_kernel<T, ADJ, DEC, SEG>), dim3(ntiles), dim3(SB), (size_t)TS * sizeof(double), ctx->stream, x, ea.decay, heads8, n, ea.d, ea.alpha, agg, out);
-    aqg_kernel_timer_end(ctx);
-    return aqg_check_launch(ctx, "ema scan");
-}
 // heads8 == nullptr: the whole column
 int dispatch_ema(aqg_ctx* ctx, const EmaArgs& ea, int t, const void* xv, const uint8_t* heads8, uint32_t n, double* out) {
     return aqg_dispatch_num(t, [&](auto tt) -> int {
@@ -184,7 +106,8 @@ int dispatch_ema(aqg_ctx* ctx, const EmaArgs& ea, int t, const void* xv, const u
         const T* x = static_cast<const T*>(xv);
         auto by = [&](auto adj, auto dec) -> int {
             constexpr bool ADJ = decltype(adj)::value, DEC = decltype(dec)::value;
-            return heads8 ? run_ema<T, ADJ, DEC, true>(ctx, ea, x, heads8, n, out) : run_ema<T, ADJ, DEC, false>(ctx, ea, x, heads8, n, out);
+            return heads8 ? prefix_pass<ema_rows<T, ADJ, DEC, true>, W_EMA>(ctx, {x, ea.decay, heads8, ea.d, ea.alpha}, n, {}, out, "ema scan")
+                          : prefix_pass<ema_rows<T, ADJ, DEC, false>, W_EMA>(ctx, {x, ea.decay, nullptr, ea.d, ea.alpha}, n, {}, out, "ema scan");
         };
         if (ea.mode == AQG_EMA_ADJUSTED) return ea.decay ? by(std::true_type{}, std::true_type{}) : by(std::true_type{}, std::false_type{});
         return ea.decay ? by(std::false_type{}, std::true_type{}) : by(std::false_type{}, std::false_type{});

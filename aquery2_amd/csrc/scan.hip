@@ -3,9 +3,11 @@
 //  sums/avgs :203-236, sumw/avgw :238-281, vars/stddevs :350-381, varw/stddevw :283-330 (D9),
 //  deltas/prev/aggnext :439-485).
 //
-// Prefix scans: reduce-then-scan over 2048-element tiles (tile reduce -> one-workgroup scan of the
-// tile aggregates -> tile scan with carry-in); inside a tile: 8 consecutive elements per lane,
-// wavefront inclusive scan (__shfl_up over 64 lanes), LDS combine of the 4 waves.
+// Prefix scans (sums / avgs, vars / stddevs, the accumulator-form prefixes of the wide windows): the reduce-then-scan pass of
+// scan_prefix.hpp over 2048-element tiles, shared with segscan.hip and ema.hip; a whole column is its SEG = false layout, whose
+// slice_of<false> carries the seed of a resumed shard.  Running min / max take the single-pass chained kernel below, which writes
+// through the same emit().  Inside a tile: 8 consecutive elements per lane, wavefront inclusive scan (__shfl_up over 64 lanes), LDS
+// combine of the 4 waves.
 // Windows (scan_window.hpp, shared with the per-group scans of segscan.hip): every tile stages its elements plus a (w-1)-element
 // halo in LDS; sums use the tile-local prefix difference S[i]-S[i-w] (exact for integers), min/max use log2(w) LDS doubling steps;
 // long min/max windows of aligned columns take the van Herk kernel below.
@@ -18,96 +20,22 @@
 #include "chain_dev.hpp"
 #include "scan_dev.hpp"
 #include "scan_window.hpp"
+#include "scan_prefix.hpp"
 
 namespace {
 using namespace aqgscan;
-
-
-// K1: aggregate of each tile
-template <class T, class ALG> __global__ void __launch_bounds__(SB) tile_reduce_kernel(const T* __restrict__ x, uint32_t n, typename ALG::A* __restrict__ tile_agg) {
-    using A = typename ALG::A;
-    __shared__ A lds_w[8];
-    uint32_t base = blockIdx.x * TS + threadIdx.x * IT, cnt;
-    T v[IT];
-    load_tile_items(x, n, base, v, cnt);
-    A a = ALG::identity();
-#pragma unroll
-    for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) a = ALG::op(a, ALG::lift(v[j]));
-    A total;
-    block_scan_excl<ALG>(a, lds_w, total);
-    if (threadIdx.x == 0) tile_agg[blockIdx.x] = total;
-}
-// K3: scan inside the tile with the carry-in; WRITER(out, i, inclusive_value)
-enum : int { W_SUMS = 0, W_AVGS = 1, W_MINS = 2, W_MAXS = 3, W_MAXP = 4, W_MINP = 5 /* W_MAXP / W_MINP: running max / min without the reference's seed (maxw / minw, w >= n) */ };
-
-// a scan that resumes a column sharded by row range (aqg_scan_resume): the sum of every earlier row in the result's LongType
-// and the number of earlier rows.  Kept apart from the tile accumulator, which is 64 bits wide for <= 4-byte integer columns
-// while the carry of a table of more than 2^32 rows is not.
-struct ScanSeed {
-    aqg_i128 i;        // integer columns
-    double d;          // floating columns (-0.0 when there is nothing to add: the only value that leaves every double unchanged)
-    uint64_t row0;     // rows before this shard (avgs divide by row0 + i + 1)
-};
-
-// writes one tile's results: `run` = fold of everything before this lane's first element
+// one sub-tile of the chained kernel through the writer of scan_prefix.hpp: `run` = fold of everything before this lane's first element
 template <class T, class ALG, int WR>
 __device__ inline void write_tile(typename ALG::A run, const T (&v)[IT], uint32_t cnt, uint32_t base, uint32_t tile_base, uint32_t n, void* __restrict__ out,
-                                  unsigned char* stage_raw, const ScanSeed& seed = ScanSeed{{0, 0}, -0.0, 0}) {
-    if constexpr (WR == W_SUMS) {
-        using O = std::conditional_t<std::is_floating_point_v<T>, double, aqg_i128>;
-        O o[IT];
+                                  unsigned char* stage_raw) {
+    using O = typename prefix_out<T, WR>::type;
+    O o[IT];
 #pragma unroll
-        for (int j = 0; j < IT; ++j) {
-            if ((uint32_t)j < cnt) run = ALG::op(run, ALG::lift(v[j]));
-            if constexpr (std::is_floating_point_v<T>) o[j] = seed.d + run; else o[j] = i128_add(seed.i, sum_alg<T>::to_i128(run));
-        }
-        store_tile_striped(static_cast<O*>(out), tile_base, o, n, reinterpret_cast<O*>(stage_raw));
-    } else if constexpr (WR == W_AVGS) {
-        double o[IT];
-#pragma unroll
-        for (int j = 0; j < IT; ++j) {
-            if ((uint32_t)j < cnt) run = ALG::op(run, ALG::lift(v[j]));
-            double sum;                                                            // (s += arr[i]) / (double)(i + 1)
-            if constexpr (std::is_floating_point_v<T>) sum = seed.d + run;
-            else {
-                const aqg_i128 t = i128_add(seed.i, sum_alg<T>::to_i128(run));
-                if constexpr (std::is_unsigned_v<T>) sum = u128_to_double(t.hi, t.lo); else sum = i128_to_double(t);
-            }
-            o[j] = sum / (double)(seed.row0 + base + j + 1);
-        }
-        store_tile_striped(static_cast<double*>(out), tile_base, o, n, reinterpret_cast<double*>(stage_raw));
-    } else {
-        T o[IT];
-#pragma unroll
-        for (int j = 0; j < IT; ++j) {
-            if ((uint32_t)j < cnt) run = ALG::op(run, ALG::lift(v[j]));
-            T r = run;
-            if constexpr (WR == W_MAXS) { T seed = dlimits<T>::min(); r = seed > r ? seed : r; }  // maxs seeds with numeric_limits<T>::min()
-            if constexpr (WR == W_MINS) { T seed = dlimits<T>::max(); r = seed < r ? seed : r; }  // mins seeds with max(): +Inf rows come out as max()
-            o[j] = r;
-        }
-        store_tile_striped(static_cast<T*>(out), tile_base, o, n, reinterpret_cast<T*>(stage_raw));
+    for (int j = 0; j < IT; ++j) {
+        if ((uint32_t)j < cnt) run = ALG::op(run, ALG::lift(v[j]));
+        o[j] = emit<T, ALG, WR, false>(run, base + j, (double)(base + j + 1), 0, ScanSeed{});
     }
-}
-
-template <class T, class ALG, int WR>
-__global__ void __launch_bounds__(SB) tile_scan_kernel(const T* __restrict__ x, uint32_t n, const typename ALG::A* __restrict__ tile_prefix,
-                                                       void* __restrict__ out, ScanSeed seed) {
-    using A = typename ALG::A;
-    __shared__ A lds_w[8];
-    extern __shared__ __align__(16) unsigned char stage_raw[];
-    uint32_t base = blockIdx.x * TS + threadIdx.x * IT, cnt;
-    T v[IT];
-    load_tile_items(x, n, base, v, cnt);
-    A a = ALG::identity();
-#pragma unroll
-    for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) a = ALG::op(a, ALG::lift(v[j]));
-    A total;
-    A run = ALG::op(tile_prefix[blockIdx.x], block_scan_excl<ALG>(a, lds_w, total));
-    if constexpr (WR == W_AVGS && sizeof(T) == 8 && std::is_integral_v<T>) {
-        if (seed.row0 == 0) seed.i = i128_add(seed.i, first_row_rounding(x[0]));   // the column's own first row (a resumed shard's carry is the caller's)
-    }
-    write_tile<T, ALG, WR>(run, v, cnt, base, blockIdx.x * TS, n, out, stage_raw, seed);
+    store_tile_striped(static_cast<O*>(out), tile_base, o, n, reinterpret_cast<O*>(stage_raw));
 }
 
 // ---- single-pass scan: chained links with decoupled look-back (protocol: chain_dev.hpp) ----------------------------------
@@ -396,65 +324,9 @@ __global__ void __launch_bounds__(1024, WPE) window_minmax_vh_kernel(const T* __
     }
 }
 
-// inclusive prefix in accumulator form (the wide-window fallback of sumw / avgw: prefix_diff_kernel)
-template <class T>
-__global__ void __launch_bounds__(SB) tile_scan_raw_kernel(const T* __restrict__ x, uint32_t n, const typename sum_alg<T>::A* __restrict__ tile_prefix,
-                                                           typename sum_alg<T>::A* __restrict__ out) {
-    using ALG = sum_alg<T>;
-    using A = typename ALG::A;
-    __shared__ A lds_w[8];
-    uint32_t base = blockIdx.x * TS + threadIdx.x * IT, cnt;
-    T v[IT];
-    load_tile_items(x, n, base, v, cnt);
-    A a = ALG::identity();
-#pragma unroll
-    for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) a = ALG::op(a, ALG::lift(v[j]));
-    A total;
-    A run = ALG::op(tile_prefix[blockIdx.x], block_scan_excl<ALG>(a, lds_w, total));
-    for (uint32_t j = 0; j < cnt; ++j) { run = ALG::op(run, ALG::lift(v[j])); out[base + j] = run; }
-}
-
-// running variance (vars / stddevs, WR 0 / 1) from the moments about x[0] (mom_alg of scan_dev.hpp) of every prefix: the tile's
-// carry-in from the tile aggregates' scan, then the lane's elements; WR 2 writes the prefix moments themselves (windows longer than
-// VAR_DIRECT_MAX_W: var_prefix_diff_kernel).  The reference updates MnX with a floating recurrence (aggregations.h:364-372).
-template <class T, int WR>
-__global__ void __launch_bounds__(SB) var_scan_kernel(const T* __restrict__ x, uint32_t n, const typename mom_alg<T>::A* __restrict__ tile_prefix, void* __restrict__ out) {
-    using ALG = mom_alg<T>;
-    using A = typename ALG::A;
-    using O = std::conditional_t<WR == 2, dpair, double>;
-    __shared__ A lds_w[8];
-    extern __shared__ __align__(16) unsigned char stage_raw[];
-    uint32_t base = blockIdx.x * TS + threadIdx.x * IT, cnt;
-    T v[IT];
-    load_tile_items(x, n, base, v, cnt);
-    A a = ALG::identity();
-#pragma unroll
-    for (int j = 0; j < IT; ++j) if ((uint32_t)j < cnt) a = ALG::op(a, ALG::lift(v[j]));
-    A total;
-    A run = ALG::op(tile_prefix[blockIdx.x], block_scan_excl<ALG>(a, lds_w, total));
-    O o[IT];
-#pragma unroll
-    for (int j = 0; j < IT; ++j) {
-        if ((uint32_t)j < cnt) run = ALG::op(run, ALG::lift(v[j]));
-        if constexpr (WR == 2) o[j] = dpair{run.s, run.q};
-        else { const double var = var_from(run.s, run.q, (double)run.n); o[j] = WR == 1 ? sqrt(var) : var; }
-    }
-    store_tile_striped(static_cast<O*>(out), blockIdx.x * TS, o, n, reinterpret_cast<O*>(stage_raw));
-}
-// the moments scan of a whole column: WR as var_scan_kernel (workspace reset and sized by the caller)
-template <class T, int WR> int run_var_scan(aqg_ctx* ctx, const T* x, uint32_t n, void* out, bool timed = true) {
-    using A = typename mom_alg<T>::A;
-    const uint32_t ntiles = aqg_ceil_div(n, TS);
-    A *agg, *chunk_tot;
-    AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
-    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles / CH + 2, &chunk_tot));
-    hipLaunchKernelGGL((tile_reduce_kernel<T, mom_alg<T>>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg);
-    launch_agg_scan<mom_alg<T>>(ctx, agg, ntiles, chunk_tot);
-    if (timed) aqg_kernel_timer_begin(ctx);
-    hipLaunchKernelGGL((var_scan_kernel<T, WR>), dim3(ntiles), dim3(SB), (size_t)TS * (WR == 2 ? sizeof(dpair) : sizeof(double)), ctx->stream, x, n, agg, out);
-    if (timed) aqg_kernel_timer_end(ctx);
-    return aqg_check_launch(ctx, "var_scan_kernel");
-}
+// Running variances (vars / stddevs) come from the moments about x[0] (mom_alg of scan_dev.hpp) of every prefix; windows longer than
+// VAR_DIRECT_MAX_W take the prefix moments themselves (W_MOM: var_prefix_diff_kernel).  The reference updates MnX with a floating
+// recurrence (aggregations.h:364-372).  Workspace of a moments pass (reset and sized by the caller):
 size_t var_ws_bytes(uint32_t n) {
     const size_t ntiles = aqg_ceil_div(n, TS);
     return (ntiles + ntiles / CH + 2) * sizeof(mom_alg<double>::A) + 8192;
@@ -469,28 +341,20 @@ template <class A> int prefix_ws(aqg_ctx* ctx, uint32_t ntiles) {
     AQG_TRY(aqg_ws_reset(ctx));
     return aqg_ws_ensure(ctx, (size_t)ntiles * (4 + 16 * PW + sizeof(A)) + ((size_t)ntiles / CH + 2) * sizeof(A) + 16384);
 }
-template <class T, int WR> constexpr size_t prefix_out_size() { return WR == W_SUMS ? (std::is_floating_point_v<T> ? 8 : 16) : WR == W_AVGS ? 8 : sizeof(T); }
 // Measured at 1e9 int32 rows (whole call): mins 1.53 ms chained vs 3.17 ms three-kernel; sums 4.34 vs 4.09; avgs 2.94 vs 2.75.
 // A 4-byte aggregate is handed over in one flagged word; the 8-byte sum of an int32 column takes two words per link and
 // the look-back then costs 1.0 ms at 1e9 rows (the same kernel without any look-back: sums 3.35 ms, avgs 2.30 ms).
 // Packing that sum into one 62-bit word changed nothing (4.43 ms): at two workgroups per CU (the 16-byte results take the
 // registers) the look-back latency itself is exposed, not the number of words.
-// So sums / avgs take the three kernels (run_prefix) and the running min / max the chain (run_chained).
-template <class T, class ALG, int WR>
-int run_prefix(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& seed = ScanSeed{{0, 0}, -0.0, 0}) {
-    using A = typename ALG::A;
-    const uint32_t ntiles = aqg_ceil_div(n, TS);
-    constexpr size_t osz = prefix_out_size<T, WR>();
-    AQG_TRY(prefix_ws<A>(ctx, ntiles));
-    A *agg3, *chunk_tot;
-    AQG_TRY(aqg_ws_get(ctx, ntiles, &agg3));
-    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles / CH + 2, &chunk_tot));
-    hipLaunchKernelGGL((tile_reduce_kernel<T, ALG>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg3);
-    launch_agg_scan<ALG>(ctx, agg3, ntiles, chunk_tot);
-    aqg_kernel_timer_begin(ctx);
-    hipLaunchKernelGGL((tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, agg3, out, seed);
-    aqg_kernel_timer_end(ctx);
-    return aqg_check_launch(ctx, "prefix scan");
+// So sums / avgs take the three kernels (column_pass) and the running min / max the chain (run_chained).
+// the three kernels over a whole column (workspace reset and sized by the caller)
+template <class T, class ALG, int WR, bool CHUNKED = true>
+int column_pass(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const char* what, const ScanSeed& seed = {}, bool timed = true) {
+    return prefix_pass<value_rows<T, ALG, false>, WR, CHUNKED>(ctx, {x, nullptr}, n, slice_of<false>{seed}, out, what, timed);
+}
+template <class T, int WR> int run_sums(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const ScanSeed& seed = {}) {
+    AQG_TRY(prefix_ws<typename sum_alg<T>::A>(ctx, aqg_ceil_div(n, TS)));
+    return column_pass<T, sum_alg<T>, WR>(ctx, x, n, out, "prefix scan", seed);
 }
 // single pass (chained tiles); mm_seed: the fold of the rows of earlier shards (null: none)
 template <class T, class ALG, int WR>
@@ -499,7 +363,7 @@ int run_chained(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const T* mm_see
     const uint32_t ntiles = aqg_ceil_div(n, TS);
     constexpr int M = chain_m<T>();
     const uint32_t nlinks = (ntiles + M - 1) / M;
-    constexpr size_t osz = prefix_out_size<T, WR>();
+    constexpr size_t osz = sizeof(typename prefix_out<T, WR>::type);
     constexpr bool is_min = WR == W_MINS || WR == W_MINP;
     AQG_TRY(prefix_ws<A>(ctx, ntiles));
     uint32_t* ctrl;
@@ -518,11 +382,7 @@ int run_chained(aqg_ctx* ctx, const T* x, uint32_t n, void* out, const T* mm_see
     AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h[1] == 0) return AQG_OK;
     // ---- a look-back timed out (should not happen): redo with the three-kernel scan -----------------------------------
-    A* agg;
-    AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
-    hipLaunchKernelGGL((tile_reduce_kernel<T, ALG>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg);
-    hipLaunchKernelGGL((agg_scan_kernel<ALG>), dim3(1), dim3(SB), 0, ctx->stream, agg, ntiles);
-    hipLaunchKernelGGL((tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), (size_t)TS * osz, ctx->stream, x, n, agg, out, ScanSeed{{0, 0}, -0.0, 0});
+    AQG_TRY((column_pass<T, ALG, WR, false>(ctx, x, n, out, nullptr, {}, /*timed=*/false)));
     if (mm_seed) hipLaunchKernelGGL((apply_seed_kernel<T, !is_min>), dim3(aqg_grid(ctx, n, SB, 4, 8)), dim3(SB), 0, ctx->stream, static_cast<T*>(out), n, *mm_seed);
     return aqg_check_launch(ctx, "prefix scan");
 }
@@ -535,16 +395,8 @@ template <class T> struct column_windows {
     whole_column seg() const { return {}; }
     int distances(whole_column&) { return AQG_OK; }                  // a row's distance to the start is its index
     int reserve(size_t bytes) { AQG_TRY(aqg_ws_reset(ctx)); return aqg_ws_ensure(ctx, bytes + var_ws_bytes(n) + 8192); }   // (var_ws_bytes: the tile aggregates of either producer)
-    int raw_prefix(A* S) {
-        const uint32_t ntiles = aqg_ceil_div(n, TS);
-        A* agg;
-        AQG_TRY(aqg_ws_get(ctx, ntiles, &agg));
-        hipLaunchKernelGGL((tile_reduce_kernel<T, sum_alg<T>>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg);
-        hipLaunchKernelGGL((agg_scan_kernel<sum_alg<T>>), dim3(1), dim3(SB), 0, ctx->stream, agg, ntiles);
-        hipLaunchKernelGGL((tile_scan_raw_kernel<T>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, agg, S);
-        return AQG_OK;
-    }
-    int moments(dpair* P) { return run_var_scan<T, 2>(ctx, x, n, P, /*timed=*/false); }
+    int raw_prefix(A* S) { return column_pass<T, sum_alg<T>, W_RAW, false>(ctx, x, n, S, nullptr, {}, /*timed=*/false); }
+    int moments(dpair* P) { return column_pass<T, mom_alg<T>, W_MOM>(ctx, x, n, P, "var_scan_kernel", {}, /*timed=*/false); }
 };
 
 } // namespace
@@ -576,8 +428,7 @@ int aqg_scan_resume(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, con
     return aqg_dispatch_num(t, [&](auto tt) -> int {
         using T = typename decltype(tt)::type;
         const T* x = static_cast<const T*>(xv);
-        if (op == AQG_SCAN_SUMS) return run_prefix<T, sum_alg<T>, W_SUMS>(ctx, x, n, out, seed);
-        return run_prefix<T, sum_alg<T>, W_AVGS>(ctx, x, n, out, seed);
+        return op == AQG_SCAN_SUMS ? run_sums<T, W_SUMS>(ctx, x, n, out, seed) : run_sums<T, W_AVGS>(ctx, x, n, out, seed);
     });
 }
 
@@ -634,8 +485,8 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
         };
         column_windows<T> col{ctx, x, n, sgrid};
         switch (op) {
-        case AQG_SCAN_SUMS: return run_prefix<T, sum_alg<T>, W_SUMS>(ctx, x, n, out);
-        case AQG_SCAN_AVGS: return run_prefix<T, sum_alg<T>, W_AVGS>(ctx, x, n, out);
+        case AQG_SCAN_SUMS: return run_sums<T, W_SUMS>(ctx, x, n, out);
+        case AQG_SCAN_AVGS: return run_sums<T, W_AVGS>(ctx, x, n, out);
         case AQG_SCAN_MINS: return run_chained<T, min_alg<T>, W_MINS>(ctx, x, n, out);
         case AQG_SCAN_MAXS: return run_chained<T, max_alg<T>, W_MAXS>(ctx, x, n, out);
         case AQG_SCAN_DELTAS: return shift(&shift_kernel<T, AQG_SCAN_DELTAS>, sgrid, w, "deltas");
@@ -696,7 +547,7 @@ int aqg_scan(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, uint32_t w
         case AQG_SCAN_VARS: case AQG_SCAN_STDDEVS: {
             AQG_TRY(aqg_ws_reset(ctx));
             AQG_TRY(aqg_ws_ensure(ctx, var_ws_bytes(n)));
-            return op == AQG_SCAN_VARS ? run_var_scan<T, 0>(ctx, x, n, out) : run_var_scan<T, 1>(ctx, x, n, out);
+            return op == AQG_SCAN_VARS ? column_pass<T, mom_alg<T>, W_VARS>(ctx, x, n, out, "var_scan_kernel") : column_pass<T, mom_alg<T>, W_STDDEVS>(ctx, x, n, out, "var_scan_kernel");
         }
         }
         return AQG_ERR_ARG;

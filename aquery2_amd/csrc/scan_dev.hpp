@@ -1,7 +1,7 @@
-// scan_dev.hpp -- tile vocabulary shared by the scan kernels (scan.hip: whole columns; segscan.hip: per-group scans over the
-// flat row-list layout of a grouping; scan_window.hpp: the sliding windows of both): accumulator algebras and the carry of a segmented
+// scan_dev.hpp -- tile vocabulary shared by the scan kernels (scan_prefix.hpp: the prefix pass of scan.hip, segscan.hip and ema.hip;
+// scan_window.hpp: the sliding windows of both layouts; scan.hip: the chained kernel): accumulator algebras and the carry of a segmented
 // scan, the workgroup exclusive scan, blocked tile loads, the LDS-transposed tile store, the variance
-// vocabulary and the scan of the tile aggregates.
+// vocabulary and the scan of the tile aggregates (K2 of the prefix pass).
 #pragma once
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"

@@ -6,8 +6,9 @@
 // server/hasher.h:181-198: descending row id inside a group).  aqg_grouped_flatten brings a column into that layout with the
 // value-carrying radix passes of postproc.hip (no row ids, no gather); a bitmap of group starts (`heads`) then makes every scan of
 // scan.hip segmented:
-//   prefix scans (sums / avgs / mins / maxs / vars / stddevs): reduce-then-scan over 2048-position tiles with the carry
-//       {value, last group start, groups so far} -- a group start resets the value;
+//   prefix scans (sums / avgs / mins / maxs / vars / stddevs, the per-group reductions, distance and group index of a position): the
+//       pass of scan_prefix.hpp in its SEG = true layout -- reduce-then-scan over 2048-position tiles with the carry
+//       {value, last group start, groups so far}; a group start resets the value;
 //   windows (sumw / avgw, minw / maxw): the kernels of scan_window.hpp in their by_group form -- tile + halo in LDS, every window
 //       clamped at its group's start (no carry between tiles: a window never reaches back further than the halo); varw / stddevw:
 //       two passes over windows of up to 64 positions, longer ones from a segmented prefix of moments about the group's first element (any w);
@@ -18,6 +19,7 @@
 #include "dev_common.hpp"
 #include "scan_dev.hpp"
 #include "scan_window.hpp"
+#include "scan_prefix.hpp"
 #include "groupby_handle.hpp"
 
 namespace {
@@ -43,13 +45,6 @@ template <class T> struct varred_alg {
     }
     __device__ static A op(A a, A b) { A r; r.s = a.s + b.s; r.q = a.q + b.q; return r; }
 };
-struct none_alg {                              // position-only scans (group index / distance to the group start of every position)
-    using A = uint32_t;
-    __device__ static uint32_t identity() { return 0; }
-    __device__ static uint32_t lift(uint8_t) { return 0; }
-    __device__ static uint32_t op(uint32_t a, uint32_t) { return a; }
-};
-
 // ---- group starts ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) heads_kernel(const uint32_t* __restrict__ off, const uint32_t* __restrict__ counts, uint32_t G,
                                                     uint32_t* __restrict__ heads, uint32_t* __restrict__ shorts, uint32_t short_w) {
@@ -59,114 +54,6 @@ __global__ void __launch_bounds__(256) heads_kernel(const uint32_t* __restrict__
         if (shorts && g < G && counts[g] <= short_w) atomicOr(&shorts[p >> 5], 1u << (p & 31));
     }
 }
-// ---- prefix family: K1 tile carries, K2 launch_agg_scan<seg_alg>, K3 results ----------------------------------------------------------
-template <class T, class ALG>
-__global__ void __launch_bounds__(SB) seg_tile_reduce_kernel(const T* __restrict__ x, uint32_t n, const uint8_t* __restrict__ heads8,
-                                                             SegCarry<typename ALG::A>* __restrict__ tile_carry) {
-    using SA = seg_alg<ALG>;
-    using C = typename SA::A;
-    __shared__ C lds_w[8];
-    uint32_t base = blockIdx.x * TS + threadIdx.x * IT, cnt;
-    T v[IT];
-    if constexpr (std::is_same_v<ALG, none_alg>) cnt = base >= n ? 0 : (n - base < (uint32_t)IT ? n - base : IT);
-    else load_tile_items(x, n, base, v, cnt);
-    const uint32_t hb = cnt ? heads8[base >> 3] : 0;
-    C a = SA::identity();
-#pragma unroll
-    for (int j = 0; j < IT; ++j) {
-        if ((uint32_t)j < cnt) {
-            if ((hb >> j) & 1) { a.v = ALG::identity(); a.s = base + j + 1; ++a.c; }
-            if constexpr (!std::is_same_v<ALG, none_alg>) a.v = ALG::op(a.v, ALG::lift(v[j]));
-        }
-    }
-    C total;
-    block_scan_excl<SA>(a, lds_w, total);
-    if (threadIdx.x == 0) tile_carry[blockIdx.x] = total;
-}
-
-enum : int { SW_SUMS = 0, SW_AVGS, SW_MINS, SW_MAXS, SW_MAXP, SW_MINP, SW_VARS, SW_STDDEVS, SW_RAW, SW_MOM, SW_DIST, SW_GID, SW_RED_SUM, SW_RED_AVG, SW_RED_MIN, SW_RED_MAX, SW_RED_VAR, SW_RED_STDDEV };
-template <class T, int WR> struct seg_out {
-    using type = std::conditional_t<WR == SW_SUMS || WR == SW_RED_SUM, std::conditional_t<std::is_floating_point_v<T>, double, aqg_i128>,
-                 std::conditional_t<WR == SW_AVGS || WR == SW_VARS || WR == SW_STDDEVS || WR == SW_RED_AVG || WR == SW_RED_VAR || WR == SW_RED_STDDEV, double,
-                 std::conditional_t<WR == SW_RAW, typename sum_alg<T>::A, std::conditional_t<WR == SW_MOM, dpair,
-                 std::conditional_t<WR == SW_DIST || WR == SW_GID, uint32_t, T>>>>>;
-};
-template <class T, class ALG, int WR>
-__global__ void __launch_bounds__(SB) seg_tile_scan_kernel(const T* __restrict__ x, uint32_t n, const uint8_t* __restrict__ heads8,
-                                                           const SegCarry<typename ALG::A>* __restrict__ tile_prefix, void* __restrict__ out) {
-    using A = typename ALG::A;
-    using SA = seg_alg<ALG>;
-    using C = typename SA::A;
-    using O = typename seg_out<T, WR>::type;
-    constexpr bool RED = WR >= SW_RED_SUM;
-    __shared__ C lds_w[8];
-    extern __shared__ __align__(16) unsigned char stage_raw[];
-    uint32_t base = blockIdx.x * TS + threadIdx.x * IT, cnt;
-    T v[IT];
-    if constexpr (std::is_same_v<ALG, none_alg>) cnt = base >= n ? 0 : (n - base < (uint32_t)IT ? n - base : IT);
-    else load_tile_items(x, n, base, v, cnt);
-    const uint32_t hb = cnt ? heads8[base >> 3] : 0;
-    uint32_t hnext = 0;                                                  // start bit of the position behind this lane's block
-    if constexpr (RED) hnext = cnt ? (heads8[(base >> 3) + 1] & 1u) : 0u;
-    C a = SA::identity();
-#pragma unroll
-    for (int j = 0; j < IT; ++j) {
-        if ((uint32_t)j < cnt) {
-            if ((hb >> j) & 1) { a.v = ALG::identity(); a.s = base + j + 1; ++a.c; }
-            if constexpr (!std::is_same_v<ALG, none_alg>) a.v = ALG::op(a.v, ALG::lift(v[j]));
-        }
-    }
-    C total;
-    const C excl = block_scan_excl<SA>(a, lds_w, total);
-    const C pre = SA::op(tile_prefix[blockIdx.x], excl);
-    A run = pre.v;
-    uint32_t s = pre.s, c = pre.c;
-    O o[IT];
-#pragma unroll
-    for (int j = 0; j < IT; ++j) {
-        if ((uint32_t)j < cnt) {
-            if ((hb >> j) & 1) { run = ALG::identity(); s = base + j + 1; ++c; }
-            if constexpr (!std::is_same_v<ALG, none_alg>) run = ALG::op(run, ALG::lift(v[j]));
-        }
-        const uint32_t p = base + j;
-        const double rows = (double)(p - s + 2);                        // rows of the group up to and including p (s = start + 1)
-        if constexpr (WR == SW_SUMS || WR == SW_RED_SUM) {
-            if constexpr (std::is_floating_point_v<T>) o[j] = run; else o[j] = sum_alg<T>::to_i128(run);
-        } else if constexpr (WR == SW_AVGS && sizeof(T) == 8 && std::is_integral_v<T>) {                            // avgs starts from the group's first row rounded to double
-            const A lead = (uint32_t)j < cnt ? first_row_rounding(x[s - 1]) : sum_alg<T>::identity();
-            o[j] = sum_alg<T>::to_double(sum_alg<T>::op(run, lead)) / rows;
-        } else if constexpr (WR == SW_AVGS || WR == SW_RED_AVG) o[j] = sum_alg<T>::to_double(run) / rows;       // (s += arr[i]) / (double)(i + 1)
-        else if constexpr (WR == SW_MAXP || WR == SW_MINP) o[j] = run;
-        else if constexpr (WR == SW_MINS || WR == SW_RED_MIN) { T seed = dlimits<T>::max(); o[j] = seed < run ? seed : run; }    // min / mins seed with max(): a +Inf group comes out as max()
-        else if constexpr (WR == SW_MAXS || WR == SW_RED_MAX) { T seed = dlimits<T>::min(); o[j] = seed > run ? seed : run; }    // max / maxs seed with numeric_limits<T>::min() (D8)
-        else if constexpr (WR == SW_VARS || WR == SW_STDDEVS) {                  // anchored moments of the group so far (mom_alg)
-            const double var = var_from(run.s, run.q, (double)run.n);
-            o[j] = WR == SW_STDDEVS ? sqrt(var) : var;
-        } else if constexpr (WR == SW_RED_VAR || WR == SW_RED_STDDEV) {          // (ssq - s * s / (FPType)(len + 1)) / (FPType)(len + 1): D9 kept
-            const double np1 = (double)(uint32_t)(p - s + 3);
-            double d;
-            if constexpr (std::is_floating_point_v<T>) d = (run.q - run.s * run.s / np1) / np1;
-            else {
-                const __int128 ss = (__int128)run.s * (__int128)run.s;                   // the reference's 128-bit LongType product (|s| < 2^63: no wrap)
-                // (uint16: the reference's sum of squares is an UNSIGNED 128-bit integer, and the int squares that wrapped negative are added
-                // to it sign-extended -- a negative 64-bit sum stands for 2^128 minus its magnitude; the rule of groupby_tail.hip's sum128)
-                double q;
-                if constexpr (std::is_same_v<T, uint16_t>) q = u128_to_double((uint64_t)(run.q >> 63), (uint64_t)run.q); else q = (double)run.q;
-                d = (q - i128_to_double(aqg_i128{(uint64_t)ss, (uint64_t)(ss >> 64)}) / np1) / np1;
-            }
-            o[j] = WR == SW_RED_STDDEV ? sqrt(d) : d;
-        } else if constexpr (WR == SW_RAW) o[j] = run;
-        else if constexpr (WR == SW_MOM) o[j] = dpair{run.s, run.q};
-        else if constexpr (WR == SW_DIST) o[j] = p - (s - 1);
-        else o[j] = c - 1;
-        if constexpr (RED) {
-            const uint32_t last = j + 1 < IT ? ((hb >> (j + 1)) & 1u) : hnext;   // the next position starts a group (bit n is set): p ends its group
-            if ((uint32_t)j < cnt && last) static_cast<O*>(out)[c - 1] = o[j];
-        }
-    }
-    if constexpr (!RED) store_tile_striped(static_cast<O*>(out), blockIdx.x * TS, o, n, reinterpret_cast<O*>(stage_raw));
-}
-
 // ---- shifts / ratios --------------------------------------------------------------------------------------------------------------
 template <class T, int OP>
 __global__ void __launch_bounds__(SB) seg_shift_kernel(const T* __restrict__ x, uint32_t n, uint32_t w, const uint32_t* __restrict__ heads,
@@ -285,25 +172,14 @@ size_t carry_ws_bytes(uint32_t n) {
     const size_t ntiles = aqg_ceil_div(n, TS);
     return ntiles * 48 + (ntiles / CH + 2) * 48 + 4096;
 }
-// one segmented prefix pass (workspace already sized): carries -> their scan -> results
+const uint8_t* heads8_of(const aqg_groupby* g) { return reinterpret_cast<const uint8_t*>(g->flat_heads); }
+// one segmented prefix pass (workspace already sized)
 template <class T, class ALG, int WR>
-int seg_prefix(aqg_ctx* ctx, aqg_groupby* g, const T* x, uint32_t n, void* out) {
-    using C = SegCarry<typename ALG::A>;
-    using O = typename seg_out<T, WR>::type;
-    static_assert(sizeof(C) <= 48, "carry_ws_bytes");
-    const uint32_t ntiles = aqg_ceil_div(n, TS);
-    const uint8_t* heads8 = reinterpret_cast<const uint8_t*>(g->flat_heads);
-    C *carry, *chunk_tot;
-    AQG_TRY(aqg_ws_get(ctx, ntiles, &carry));
-    AQG_TRY(aqg_ws_get(ctx, (size_t)ntiles / CH + 2, &chunk_tot));
-    hipLaunchKernelGGL((seg_tile_reduce_kernel<T, ALG>), dim3(ntiles), dim3(SB), 0, ctx->stream, x, n, heads8, carry);
-    launch_agg_scan<seg_alg<ALG>>(ctx, carry, ntiles, chunk_tot);
-    aqg_kernel_timer_begin(ctx);
-    hipLaunchKernelGGL((seg_tile_scan_kernel<T, ALG, WR>), dim3(ntiles), dim3(SB), WR >= SW_RED_SUM ? 0 : (size_t)TS * sizeof(O), ctx->stream, x, n, heads8, carry, out);
-    aqg_kernel_timer_end(ctx);
-    return aqg_check_launch(ctx, "segmented prefix scan");
+int seg_pass(aqg_ctx* ctx, aqg_groupby* g, const T* x, uint32_t n, void* out) {
+    static_assert(sizeof(SegCarry<typename ALG::A>) <= 48, "carry_ws_bytes");
+    return prefix_pass<value_rows<T, ALG, true>, WR>(ctx, {x, heads8_of(g)}, n, {}, out, "segmented prefix scan");
 }
-int dist_column(aqg_ctx* ctx, aqg_groupby* g, uint32_t n, uint32_t* D) { return seg_prefix<uint8_t, none_alg, SW_DIST>(ctx, g, nullptr, n, D); }
+int dist_column(aqg_ctx* ctx, aqg_groupby* g, uint32_t n, uint32_t* D) { return prefix_pass<position_rows, W_DIST>(ctx, {heads8_of(g)}, n, {}, D, "segmented prefix scan"); }
 
 // what window_scan (scan_window.hpp) asks of a layout, for the flat layout of a grouping
 template <class T> struct group_windows {
@@ -311,8 +187,8 @@ template <class T> struct group_windows {
     aqg_ctx* ctx; aqg_groupby* g; const T* x; uint32_t n; unsigned row_grid;
     by_group seg() const { return {g->flat_heads, nullptr}; }
     int reserve(size_t) { return AQG_OK; }                           // the caller sized the workspace (scan_ws_bytes) and it is not reset in here
-    int raw_prefix(typename sum_alg<T>::A* S) { return seg_prefix<T, sum_alg<T>, SW_RAW>(ctx, g, x, n, S); }
-    int moments(dpair* P) { return seg_prefix<T, mom_alg<T>, SW_MOM>(ctx, g, x, n, P); }
+    int raw_prefix(typename sum_alg<T>::A* S) { return seg_pass<T, sum_alg<T>, W_RAW>(ctx, g, x, n, S); }
+    int moments(dpair* P) { return seg_pass<T, mom_alg<T>, W_MOM>(ctx, g, x, n, P); }
     int distances(by_group& s) {
         uint32_t* D;
         AQG_TRY(aqg_ws_get(ctx, n, &D));
@@ -359,12 +235,12 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
             return aqg_check_launch(ctx, what);
         };
         switch (op) {
-        case AQG_SCAN_SUMS: return seg_prefix<T, sum_alg<T>, SW_SUMS>(ctx, g, x, n, out);
-        case AQG_SCAN_AVGS: return seg_prefix<T, sum_alg<T>, SW_AVGS>(ctx, g, x, n, out);
-        case AQG_SCAN_MINS: return seg_prefix<T, min_alg<T>, SW_MINS>(ctx, g, x, n, out);
-        case AQG_SCAN_MAXS: return seg_prefix<T, max_alg<T>, SW_MAXS>(ctx, g, x, n, out);
-        case AQG_SCAN_VARS: return seg_prefix<T, mom_alg<T>, SW_VARS>(ctx, g, x, n, out);
-        case AQG_SCAN_STDDEVS: return seg_prefix<T, mom_alg<T>, SW_STDDEVS>(ctx, g, x, n, out);
+        case AQG_SCAN_SUMS: return seg_pass<T, sum_alg<T>, W_SUMS>(ctx, g, x, n, out);
+        case AQG_SCAN_AVGS: return seg_pass<T, sum_alg<T>, W_AVGS>(ctx, g, x, n, out);
+        case AQG_SCAN_MINS: return seg_pass<T, min_alg<T>, W_MINS>(ctx, g, x, n, out);
+        case AQG_SCAN_MAXS: return seg_pass<T, max_alg<T>, W_MAXS>(ctx, g, x, n, out);
+        case AQG_SCAN_VARS: return seg_pass<T, mom_alg<T>, W_VARS>(ctx, g, x, n, out);
+        case AQG_SCAN_STDDEVS: return seg_pass<T, mom_alg<T>, W_STDDEVS>(ctx, g, x, n, out);
         case AQG_SCAN_VARW: case AQG_SCAN_STDDEVW: case AQG_SCAN_SUMW: case AQG_SCAN_AVGW:
             return window_scan(ctx, grp, op, x, n, w > n ? n : w, out);                 // (a window is clamped by its group anyway)
         case AQG_SCAN_DELTAS: return al16 ? shift4(&seg_shift4_kernel<T, AQG_SCAN_DELTAS>, "deltas (grouped)") : shift(&seg_shift_kernel<T, AQG_SCAN_DELTAS>, "deltas (grouped)");
@@ -374,7 +250,7 @@ int scan_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const void* xv, uint3
         case AQG_SCAN_MINW: case AQG_SCAN_MAXW: {
             const bool is_max = op == AQG_SCAN_MAXW;
             // the deque never expires anything when w == 0 or w >= n: the running min / max of the group (no seed)
-            if (w == 0 || w >= n) return is_max ? seg_prefix<T, max_alg<T>, SW_MAXP>(ctx, g, x, n, out) : seg_prefix<T, min_alg<T>, SW_MINP>(ctx, g, x, n, out);
+            if (w == 0 || w >= n) return is_max ? seg_pass<T, max_alg<T>, W_MAXP>(ctx, g, x, n, out) : seg_pass<T, min_alg<T>, W_MINP>(ctx, g, x, n, out);
             return window_scan(ctx, grp, op, x, n, w, out);
         }
         }
@@ -407,7 +283,7 @@ int aqg_flat_gid(aqg_ctx* ctx, aqg_groupby* g, const uint32_t** gid) {
         AQG_TRY(aqg_ws_reset(ctx));
         AQG_TRY(aqg_ws_ensure(ctx, carry_ws_bytes(n) * 2 + 65536));
         AQG_TRY(aqg_dev_realloc(ctx, &g->flat_gid, &g->cap_flat_gid, ((size_t)n + 4) * 4));
-        AQG_TRY((seg_prefix<uint8_t, none_alg, SW_GID>(ctx, g, nullptr, n, g->flat_gid)));
+        AQG_TRY((prefix_pass<position_rows, W_GID>(ctx, {heads8_of(g)}, n, {}, g->flat_gid, "segmented prefix scan")));
         g->flat_gid_valid = true;
     }
     *gid = g->flat_gid;
@@ -489,10 +365,10 @@ int aqg_grouped_reduce_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const v
             using T = typename decltype(tt)::type;
             const T* x = static_cast<const T*>(xflat);
             switch (op) {
-            case AQG_RED_SUM: return seg_prefix<T, sum_alg<T>, SW_RED_SUM>(ctx, g, x, n, out_dev);
-            case AQG_RED_AVG: return seg_prefix<T, sum_alg<T>, SW_RED_AVG>(ctx, g, x, n, out_dev);
-            case AQG_RED_MIN: return seg_prefix<T, min_alg<T>, SW_RED_MIN>(ctx, g, x, n, out_dev);
-            default: return seg_prefix<T, max_alg<T>, SW_RED_MAX>(ctx, g, x, n, out_dev);
+            case AQG_RED_SUM: return seg_pass<T, sum_alg<T>, W_RED_SUM>(ctx, g, x, n, out_dev);
+            case AQG_RED_AVG: return seg_pass<T, sum_alg<T>, W_RED_AVG>(ctx, g, x, n, out_dev);
+            case AQG_RED_MIN: return seg_pass<T, min_alg<T>, W_RED_MIN>(ctx, g, x, n, out_dev);
+            default: return seg_pass<T, max_alg<T>, W_RED_MAX>(ctx, g, x, n, out_dev);
             }
         });
     }
@@ -501,7 +377,7 @@ int aqg_grouped_reduce_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int t, const v
             using T = typename decltype(tt)::type;
             if constexpr (sizeof(T) <= 4 || std::is_floating_point_v<T>) {
                 const T* x = static_cast<const T*>(xflat);
-                return op == AQG_RED_VAR ? seg_prefix<T, varred_alg<T>, SW_RED_VAR>(ctx, g, x, n, out_dev) : seg_prefix<T, varred_alg<T>, SW_RED_STDDEV>(ctx, g, x, n, out_dev);
+                return op == AQG_RED_VAR ? seg_pass<T, varred_alg<T>, W_RED_VAR>(ctx, g, x, n, out_dev) : seg_pass<T, varred_alg<T>, W_RED_STDDEV>(ctx, g, x, n, out_dev);
             } else return AQG_ERR_DTYPE;
         });
     }

@@ -160,7 +160,7 @@ def _dense():
 
 # Groups of MANY rows that start on a tile border (0, 4096, 8192), on a lane-block border (8), in a tile's last position (2047: every
 # row behind the first sits in the next tile and learns the start from the tile's carry) and inside a lane block (6149, 8292): where
-# seg_tile_scan_kernel re-reads the group's first row for avgs of 8-byte integers.  (In "borders" the issue's starts 0, 8, 2047 and 2048 are
+# prefix_scan_kernel re-reads the group's first row for avgs of 8-byte integers.  (In "borders" the issue's starts 0, 8, 2047 and 2048 are
 # followed by starts at 1, 9, 2048 and 2049: one-row groups, whose avgs is the first row rounded whatever the kernel adds.)
 FIRST_ROW_STARTS = (0, 8, 2047, 4096, 6149, 8192, 8292)
 

@@ -107,7 +107,7 @@ def test_every_op_on_every_route(gpu, oracle, builds, lname, dt, fam):
 def test_avgs_sums_from_the_groups_first_row_rounded_to_double(gpu, oracle, builds, dt):
     """`s = ret[0] = arr[0]` per group: every first row a double cannot hold as the first flat row of groups of many rows that start on a
     tile border, on a lane-block border, in a tile's last position (its other rows sit in the next tile) and inside a lane block;
-    seg_tile_scan_kernel reads that row back (x[s - 1]) for every later row.  The rows behind it are chosen so that each mean shows
+    prefix_scan_kernel reads that row back (x[s - 1]) for every later row.  The rows behind it are chosen so that each mean shows
     whether the rounding was carried (grouped_scan_cases.planted_first_rows; the CPU test of the same name shows it start by start)."""
     lay, gb = builds("first-rows")
     for first, flat in gc.planted_first_rows(lay, dt):
@@ -190,13 +190,13 @@ def test_two_level_carry_scan(gpu):
     assert ex.same(gpu.grouped_reduce_flat(gb, ck.RED_AVG, d), np.array([float(s) / float(c) for s, c in zip(sums, lay.sizes)]))
     assert ex.same(gpu.grouped_reduce_flat(gb, ck.RED_MIN, d), np.array([flat[r].min() for r in runs], np.int8))
     assert ex.same(gpu.grouped_reduce_flat(gb, ck.RED_MAX, d), np.array([flat[r].max() for r in runs], np.int8))
-    # var: (ssq - s * s / (len + 1)) / (len + 1) with exact integer sums, the reference's formula (seg_tile_scan_kernel, SW_RED_VAR)
+    # var: (ssq - s * s / (len + 1)) / (len + 1) with exact integer sums, the reference's formula (prefix_scan_kernel, W_RED_VAR)
     ssq = [int((flat[r].astype(np.int64) ** 2).sum()) for r in runs]
     var = np.array([(float(q) - float(s * s) / float(c + 1)) / float(c + 1) for s, q, c in zip(sums, ssq, lay.sizes.tolist())])
     tol = np.array([4 * 2.0 ** -53 * (q + s * s / (c + 1)) / (c + 1) for s, q, c in zip(sums, ssq, lay.sizes.tolist())])   # four roundings of terms of at most q, s^2 / (len + 1)
     got = gpu.grouped_reduce_flat(gb, ck.RED_VAR, d)
     assert np.all(np.abs(got - var) <= tol), (got, var, tol)
-    # a window through HBM: its distance column (none_alg, SW_DIST) takes the same carry scan
+    # a window through HBM: its distance column (position_rows, W_DIST) takes the same carry scan
     w = gc.first_hbm_w(gc.minmax_route, np.int8)
     got = gpu.grouped_scan(gb, ck.SCAN_MINW, d, w, flat=True)
     for r in runs:                                        # behind every start, where the window closes, anywhere, and the group's last rows
