@@ -67,6 +67,19 @@ EMA_PROTOTYPES = {
     "aqg_decay_from_times": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p],
     "aqg_grouped_decay_from_times_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p],
 }
+# ctypes prototypes of the time-range windows (applied by load_library)
+RANGEW_COUNT, RANGEW_SUM, RANGEW_AVG, RANGEW_MIN, RANGEW_MAX = range(5)
+RANGEW_OPEN, RANGEW_CLOSED = 0, 1
+RANGEW_PROTOTYPES = {
+    "aqg_rangew_out_dtype": [C.c_int, C.c_int],
+    "aqg_rangew_bounds": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_double, C.c_int, C.c_void_p],
+    "aqg_grouped_rangew_bounds_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p],
+    "aqg_rangew_fold": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "aqg_rangew": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_grouped_rangew": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_grouped_rangew_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_rangew_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 # ctypes prototypes of the count-distinct entries (applied by load_library)
 DISTINCT_PROTOTYPES = {
     "aqg_count_distinct": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)],
@@ -133,7 +146,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -780,6 +793,58 @@ class Device:
         else:
             self._chk(self.lib.aqg_decay_from_times(self.ctx, td.tag, td.ptr, td.n, float(halflife), out.ptr), "aqg_decay_from_times")
         return out if keep else out.to_host()
+
+    # -- time-range windows (binary-searched bounds + a combining-only block tree: include/aqg.h, time-range windows section)
+    def rangew_out(self, op, x, n):
+        """an empty device column for the result of `op` over the column x (None for RANGEW_COUNT)"""
+        tag = self.lib.aqg_rangew_out_dtype(op, x.tag if x is not None else INT32)
+        if tag == ERROR:
+            raise AqgError("aqg_rangew_out_dtype", 2)
+        return self.empty(n, TAG2NP[tag])
+
+    def rangew_bounds(self, t, span, frame=RANGEW_OPEN, gb=None, keep=False, out=None):
+        """lo[i] = the first position of row i's window (rows within `span` of t[i], ending at i); gb: `t` is in the flat layout of
+        that build and every window is clamped at its group's start"""
+        td = self._dev(t)
+        out = out if out is not None else self.empty(td.n, np.uint32)
+        if gb is not None:
+            self._chk(self.lib.aqg_grouped_rangew_bounds_flat(self.ctx, gb.h, td.tag, td.ptr, float(span), frame, out.ptr), "aqg_grouped_rangew_bounds_flat")
+        else:
+            self._chk(self.lib.aqg_rangew_bounds(self.ctx, td.tag, td.ptr, td.n, float(span), frame, out.ptr), "aqg_rangew_bounds")
+        return out if keep else out.to_host()
+
+    def rangew_fold(self, op, x, lo, keep=False, out=None):
+        """out[i] = op over x[lo[i] .. i] (lo[i] > i is clamped to i); x may be None for RANGEW_COUNT"""
+        xd = self._dev(x) if x is not None else None
+        ld = self._dev(np.asarray(lo, np.uint32) if not isinstance(lo, DevBuf) else lo)
+        out = out if out is not None else self.rangew_out(op, xd, ld.n)
+        self._chk(self.lib.aqg_rangew_fold(self.ctx, op, xd.tag if xd else INT32, xd.ptr if xd else None, ld.n, ld.ptr, out.ptr), "aqg_rangew_fold")
+        return out if keep else out.to_host()
+
+    def rangew(self, op, t, span, x=None, frame=RANGEW_OPEN, keep=False, out=None):
+        """op over every row's time window of a column: the rows within `span` of t[i], ending at row i"""
+        td = self._dev(t)
+        xd = self._dev(x) if x is not None else None
+        out = out if out is not None else self.rangew_out(op, xd, td.n)
+        self._chk(self.lib.aqg_rangew(self.ctx, op, td.tag, td.ptr, float(span), frame, xd.tag if xd else INT32, xd.ptr if xd else None, td.n, out.ptr), "aqg_rangew")
+        return out if keep else out.to_host()
+
+    def grouped_rangew(self, gb, op, t, span, x=None, frame=RANGEW_OPEN, flat=False, keep=False, out=None):
+        """rangew within every group of a build, in the flat layout: `t` and `x` in row layout, or (flat=True) already in the flat layout"""
+        td = self._dev(t)
+        xd = self._dev(x) if x is not None else None
+        out = out if out is not None else self.rangew_out(op, xd, td.n)
+        fn = self.lib.aqg_grouped_rangew_flat if flat else self.lib.aqg_grouped_rangew
+        self._chk(fn(self.ctx, gb.h, op, td.tag, td.ptr, float(span), frame, xd.tag if xd else INT32, xd.ptr if xd else None, out.ptr), "aqg_grouped_rangew")
+        return out if keep else out.to_host()
+
+    def rangew_last(self):
+        """(levels, rows per block at each level, rising steps, falling steps): the geometry of the last fold and the step counters
+        of the last bounds pass; synchronises the stream"""
+        nl, up, down = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        br = (C.c_uint32 * 8)()
+        self._chk(self.lib.aqg_rangew_last(self.ctx, C.byref(nl), br, C.byref(up), C.byref(down)), "aqg_rangew_last")
+        return nl.value, list(br)[:nl.value], up.value, down.value
 
     # -- count distinct (include/aqg.h, count distinct section)
     def count_distinct(self, x):

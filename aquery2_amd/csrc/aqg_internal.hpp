@@ -60,7 +60,11 @@ struct aqg_ctx {
     uint32_t join_routes = 0, join_groups = 0, join_slots = 0;   // aqg_join_keys_*: form and route, distinct build tuples and table slots of the last call (aqg_join_last)
     uint32_t asof_routes = 0, asof_groups = 0, asof_passes = 0;   // aqg_join_asof: routes, distinct build tuples and the ordering step's digit passes of the last call (aqg_join_asof_last)
     uint32_t winq_tile = 0, winq_halo = 0;       // aqg_window_quantiles*: rows per workgroup and halo rows of the last call (aqg_window_quantiles_last)
-    uint32_t str_route = 0, str_mismatch = 0;    // aqg_str_encode: the route of the last call and whether its verify kernel saw a mismatch (aqg_str_encode_last)
+    // aqg_rangew*: the packed step counters of the last bounds call (rising steps in the low word, falling in the high one) and the
+    // row count of the last fold, from which aqg_rangew_last derives the block tree's geometry
+    unsigned long long* rangew_steps = nullptr;
+    uint32_t rangew_fold_n = 0;
+    uint32_t str_route = 0, str_mismatch = 0;   // aqg_str_encode: the route of the last call and whether its verify kernel saw a mismatch (aqg_str_encode_last)
     // pinned host staging for small results
     void* host_stage = nullptr;
     size_t host_stage_cap = 0;

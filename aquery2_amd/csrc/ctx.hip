@@ -109,6 +109,7 @@ void aqg_ctx_destroy(aqg_ctx* ctx) {
     if (ctx->select_ctl) hipFree(ctx->select_ctl);
     if (ctx->distinct_scratch) aqg_groupby_destroy(ctx->distinct_scratch);      // (its buffers go to the pool, freed below)
     if (ctx->distinct_ctl) hipFree(ctx->distinct_ctl);
+    if (ctx->rangew_steps) hipFree(ctx->rangew_steps);
     if (ctx->distinct_pairs) hipFree(ctx->distinct_pairs);
     for (auto& e : ctx->pool) hipFree(e.first);
     if (ctx->pool_big) hipFree(ctx->pool_big);

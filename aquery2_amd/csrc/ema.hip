@@ -15,6 +15,7 @@
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
 #include "scan_prefix.hpp"
+#include "stamps_dev.hpp"
 #include "groupby_handle.hpp"
 
 namespace {
@@ -47,16 +48,7 @@ template <class T, bool ADJ, bool DEC, bool SEG_> struct ema_rows : lane_block<S
 };
 
 // ---- decay[i] = 2^(-|t[i] - t[i-1]| / halflife), decay[0] = 1 --------------------------------------------------------------------------
-// days of a civil date (proleptic Gregorian) / milliseconds of a time of day: what a difference of the reference's date_t / time_t means
-struct ema_date { unsigned char day, month; short year; };
-struct ema_time { unsigned int ms; unsigned char seconds, minutes, hours, pad; };
-__device__ inline int64_t stamp_of(ema_date t) {
-    const int64_t y = (int64_t)t.year - (t.month <= 2), m = t.month, dd = t.day;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400, yoe = y - era * 400;
-    const int64_t doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + dd - 1, doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + doe;
-}
-__device__ inline int64_t stamp_of(ema_time t) { return (((int64_t)t.hours * 60 + t.minutes) * 60 + t.seconds) * 1000 + t.ms; }
+// (the stamps of DATE / TIME columns: stamps_dev.hpp)
 // |a - b| as an unevaluated sum hi + lo of two doubles, EXACT: integers subtract in integer arithmetic first (a difference of 64-bit stamps
 // has up to 64 bits), floating columns take the rounding error of their subtraction along
 struct dd { double hi, lo; };

@@ -372,6 +372,63 @@ int aqg_grouped_ema_flat(aqg_ctx* ctx, struct aqg_groupby* g, int mode, int t, c
 int aqg_decay_from_times(aqg_ctx* ctx, int t, const void* times, uint32_t n, double halflife, double* decay_out);
 int aqg_grouped_decay_from_times_flat(aqg_ctx* ctx, struct aqg_groupby* g, int t, const void* times_flat, double halflife, double* decay_flat);
 
+/* ---- time-range windows: sumr / avgr / minr / maxr / countr ------------------
+ * Windows measured in TIME, not in rows: "traded volume of the last 5 s by symbol", SQL RANGE BETWEEN :span PRECEDING AND CURRENT ROW,
+ * pandas rolling("5s"), the window half of kdb's wj.  THE REFERENCE HAS NO SUCH FUNCTION; the contract is this comment, held by the
+ * exact model tests/timewin_model.py.
+ *
+ * SLICE   the whole column, or one group's rows in the flat layout of an aqg_groupby_build handle (descending row ids, as every grouped
+ *         scan sees them).
+ * WINDOW  of row i: the rows [lo_i, i] of its slice, lo_i = the smallest position of the slice from which EVERY row up to i lies within
+ *         `span` of t[i].  The window ends at row i itself (pandas rolling, kdb): later rows with the same stamp -- the peers a SQL RANGE
+ *         frame would add -- are NOT in it.  Row i is always in its own window.
+ * DISTANCE d(i, j) = |t[i] - t[j]|.  Integer, AQG_DATE (days) and AQG_TIME (milliseconds) stamps: exact in unsigned 64-bit arithmetic,
+ *         larger minus smaller, never t[i] - span (nothing wraps at the ends of int64 / uint64).  Floating stamps: the one rounded
+ *         subtraction in double, which is monotone in t[j].  The absolute value lets ascending columns and descending ones (the order
+ *         of a group's rows in the flat layout of an ascending column) go through one code path.
+ * FRAME   AQG_RANGEW_OPEN: d < span (pandas closed="right", the default); AQG_RANGEW_CLOSED: d <= span (SQL RANGE .. PRECEDING, pandas
+ *         closed="both").  For integer / DATE / TIME stamps the span becomes ONE exact limit "in window <=> d <= dmax": CLOSED dmax =
+ *         floor(span), OPEN dmax = ceil(span) - 1, both saturated at 2^64 - 1.  CLOSED needs span >= 0, OPEN span > 0; +Inf is allowed
+ *         (the running sums / mins / maxs of the slice); NaN or anything else AQG_ERR_ARG.
+ * ORDER   within one call the stamps of every slice run in one direction, all non-decreasing or all non-increasing.  When they do
+ *         not, every lo still lies in [slice start, i], the outputs are unspecified and nothing is read out of bounds.  The bounds pass
+ *         counts the rising and the falling steps inside slices; aqg_rangew_last returns both, and a caller who cares checks that one
+ *         of them is 0.
+ * AGGREGATES, folded by COMBINING ONLY -- nothing is subtracted back out, no prefix difference is taken; len_i = i - lo_i + 1:
+ *   AQG_RANGEW_COUNT   AQG_UINT32        len_i (x may be NULL, t is ignored)
+ *   AQG_RANGEW_SUM     aqg_long_type(t)  integers exact (128 bits); floating: a sum of exactly the window's rows in double, in a
+ *                                        bracketing fixed by n and the positions: |got - exact| <= m u / (1 - m u) sum |x_j| over the
+ *                                        window, m = len_i - 1, u = 2^-53 (the bound of ANY order of summation), while sum |x_j| < 2^1023
+ *   AQG_RANGEW_AVG     AQG_DOUBLE        integers: the exact sum rounded to double, over len_i; floating: the SUM value over len_i
+ *   AQG_RANGEW_MIN/MAX t                 an element of the window, bit for bit (which zero of -0.0 / +0.0 is unspecified)
+ *   Non-finite rows act on exactly the windows that hold them: a NaN row gives NaN, +Inf and -Inf together NaN, one kind of Inf that
+ *   Inf; every other window is unaffected (what sumw cannot promise, and a rolling add-and-remove gets wrong after a large value
+ *   leaves).  MIN / MAX of a window that holds a NaN are unspecified.  Results are bit-reproducible from call to call; the column
+ *   form and the grouped form need not agree bit for bit on floating sums.
+ * x: the dtypes of aqg_scan; t (stamps): those of aqg_decay_from_times; anything else AQG_ERR_DTYPE.  AQG_ERR_ARG: out overlapping an
+ * input, a handle not made by aqg_groupby_build, a bad op or frame, a NULL column with rows.  Every error returns with nothing
+ * written; n == 0 or G == 0 is AQG_OK.  Asynchronous on the context's stream, no host round trip, scratch from the context workspace,
+ * and the number of launches does not depend on n, G or the window lengths.
+ *   aqg_rangew_bounds / aqg_grouped_rangew_bounds_flat   lo[i] = first position of row i's window, in the layout the stamps are in
+ *   aqg_rangew_fold         out[i] = op over x[lo[i] .. i]; knows nothing of groups, the bounds carry them; lo[i] > i is clamped to i.
+ *                           Public so that several aggregates over one frame share one search.
+ *   aqg_rangew              bounds + fold of a column
+ *   aqg_grouped_rangew      the same per group, stamps and values in ROW layout (brought into the flat layout in workspace)
+ *   aqg_grouped_rangew_flat the same over columns already in the flat layout; out in the flat layout either way
+ *   aqg_rangew_last         synchronises the stream; the geometry of the last fold -- *nlevels levels, level k in blocks of
+ *                           block_rows[k] rows (8 words, 0 beyond the levels), the top level one block -- and the steps of the last
+ *                           bounds pass                                                                                          */
+enum { AQG_RANGEW_COUNT = 0, AQG_RANGEW_SUM = 1, AQG_RANGEW_AVG = 2, AQG_RANGEW_MIN = 3, AQG_RANGEW_MAX = 4 };
+enum { AQG_RANGEW_OPEN = 0, AQG_RANGEW_CLOSED = 1 };
+int aqg_rangew_out_dtype(int op, int t);
+int aqg_rangew_bounds(aqg_ctx* ctx, int tt, const void* times, uint32_t n, double span, int frame, uint32_t* lo_out);
+int aqg_grouped_rangew_bounds_flat(aqg_ctx* ctx, struct aqg_groupby* g, int tt, const void* times_flat, double span, int frame, uint32_t* lo_flat_out);
+int aqg_rangew_fold(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, const uint32_t* lo, void* out);
+int aqg_rangew(aqg_ctx* ctx, int op, int tt, const void* times, double span, int frame, int t, const void* x, uint32_t n, void* out);
+int aqg_grouped_rangew(aqg_ctx* ctx, struct aqg_groupby* g, int op, int tt, const void* times_row, double span, int frame, int t, const void* x_row, void* out_flat);
+int aqg_grouped_rangew_flat(aqg_ctx* ctx, struct aqg_groupby* g, int op, int tt, const void* times_flat, double span, int frame, int t, const void* xflat, void* out_flat);
+int aqg_rangew_last(aqg_ctx* ctx, uint32_t* nlevels, uint32_t* block_rows /* [8] */, uint32_t* steps_up, uint32_t* steps_down);
+
 /* ---- count distinct ----------------------------------------------------------
  * `count(distinct x)`: the generator emits `(x).distinct_size()` (common/types.py:271-277), under GROUP BY `(x[val]).distinct_size()`
  * inside the generated loop (engine/ast.py:749-784).  Replaces vector_type::distinct_size (server/vector_type.hpp:153-174) and

@@ -155,6 +155,38 @@ template <class T, template <typename...> class VT, class Ret> inline void devic
     dev::check(aqg_decay_from_times(rt.ctx(), dev::tag_of<std::remove_cv_t<T>>::value, in.d, n, halflife, static_cast<double*>(dout)), "aqg_decay_from_times");
     if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
 }
+// ret = op over every row's time window (include/aqg.h, time-range windows section): the rows within `span` of t[i], ending at row i.
+// x == nullptr: AQG_RANGEW_COUNT.  When the stamps (and the values) are per-group temporaries of the generated loop that are ALL of one
+// group of the same grouping, the call is answered for all groups at once (Runtime::vcol_rangew: one search per (t, span, frame), one
+// fold per aggregate) and `ret` becomes this group's slice; any other vector -- a `subvec` view shorter than its group among them --
+// goes through aqg_rangew on its own rows.
+template <class Ret> inline void device_rangew(int op, double span, bool closed, const void* t, bool t_borrowed, int ttag, size_t tsz,
+                                               const void* x, bool x_borrowed, int xtag, size_t xsz, uint32_t n, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    auto& rt = dev::Runtime::get();
+    if (n == 0) return;
+    const int frame = closed ? AQG_RANGEW_CLOSED : AQG_RANGEW_OPEN;
+    if (aqg_rangew_out_dtype(op, x ? xtag : (int)AQG_INT32) != dev::tag_of<RT>::value) { std::fprintf(stderr, "[aquery-mi355x] time-range window result element type mismatch (op %d)\n", op); std::abort(); }
+    if (rt.deferred_whole(t, n) && (!x || rt.deferred_whole(x, n))) {
+        dev::Entry* et = rt.deferred_at(t);
+        dev::Entry* ex = x ? rt.deferred_at(x) : nullptr;
+        if (!ex || (ex->dgroup == et->dgroup && ex->dg == et->dg)) {
+            dev::GroupCtx* gc = et->dgroup;
+            const uint32_t g = et->dg;
+            const int r = rt.vcol_rangew(gc, op, et->dv, ex ? ex->dv : -1, span, frame);
+            rt.defer_slice(ret.container, (size_t)n * sizeof(RT), gc, g, r);
+            if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+            return;
+        }
+    }
+    void* dout = rt.result(ret.container, (size_t)n * sizeof(RT));
+    dev::In it(t, (size_t)n * tsz, t_borrowed);
+    if (x) {
+        dev::In ix(x, (size_t)n * xsz, x_borrowed);
+        dev::check(aqg_rangew(rt.ctx(), op, ttag, it.d, span, frame, xtag, ix.d, n, dout), "aqg_rangew");
+    } else dev::check(aqg_rangew(rt.ctx(), op, ttag, it.d, span, frame, AQG_INT32, nullptr, n, dout), "aqg_rangew");
+    if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+}
 // ret[i] = the row of rank floor (AQG_SEL_LOWER) / ceil (AQG_SEL_UPPER) of num (len - 1) / den of the last len = min(w, i + 1) elements of
 // arr in ascending order (include/aqg.h, moving quantiles section).  A per-group temporary of the generated loop is answered for ALL groups
 // by one aqg_grouped_window_quantiles_flat (Runtime::vcol_window_quantile) and `ret` becomes this group's slice of that result, exactly as
@@ -402,6 +434,33 @@ AQ_EMAD(ewmad, AQG_EMA_ADJUSTED)
 AQ_DECAY(decay)
 AQ_DECAY(decayt)
 #undef AQ_DECAY
+
+// sumr / avgr / minr / maxr(span, t, x [, closed]) and countr(span, t [, closed]): the aggregates of the rows within `span` of t[i] that
+// end at row i -- windows measured in time, not rows (pandas rolling("5s"), SQL RANGE BETWEEN span PRECEDING AND CURRENT ROW, kdb's wj);
+// closed = false: |t[i] - t[j]| < span, true: <= span.  The reference's header has none of them (include/aqg.h, time-range windows section).
+#define AQ_RANGEW(name, code, RET_T)                                                                              \
+    template <class S, class TT, template <typename...> class VTT, class T, template <typename...> class VT, class Ret,           \
+              std::enable_if_t<aq::is_vt<VT, T> && aq::is_vt<VTT, TT> && std::is_arithmetic_v<S> && !std::is_same_v<std::decay_t<Ret>, bool>>* = nullptr> \
+    void name(S span, const VTT<TT>& t, const VT<T>& x, Ret& ret, bool closed = false) {                          \
+        if (t.size != x.size) aq::dev::check(AQG_ERR_ARG, #name ": the stamps and the values differ in length");  \
+        aq::device_rangew(code, (double)span, closed, t.container, t.capacity == 0, aq::dev::tag_of<std::remove_cv_t<TT>>::value, sizeof(TT), \
+                          x.container, x.capacity == 0, aq::dev::tag_of<std::remove_cv_t<T>>::value, sizeof(T), x.size, ret);   \
+    }                                                                                                             \
+    template <class S, class TT, template <typename...> class VTT, class T, template <typename...> class VT,      \
+              std::enable_if_t<aq::is_vt<VT, T> && aq::is_vt<VTT, TT> && std::is_arithmetic_v<S>>* = nullptr>     \
+    inline decayed_t<VT, RET_T> name(S span, const VTT<TT>& t, const VT<T>& x, bool closed = false) { decayed_t<VT, RET_T> ret(x.size); name(span, t, x, ret, closed); return ret; }
+AQ_RANGEW(sumr, AQG_RANGEW_SUM, types::GetLongType<T>)
+AQ_RANGEW(avgr, AQG_RANGEW_AVG, aq::fp_of_long<T>)
+AQ_RANGEW(minr, AQG_RANGEW_MIN, T)
+AQ_RANGEW(maxr, AQG_RANGEW_MAX, T)
+#undef AQ_RANGEW
+template <class S, class TT, template <typename...> class VTT, class Ret, std::enable_if_t<aq::is_vt<VTT, TT> && std::is_arithmetic_v<S> && !std::is_same_v<std::decay_t<Ret>, bool>>* = nullptr>
+void countr(S span, const VTT<TT>& t, Ret& ret, bool closed = false) {
+    aq::device_rangew(AQG_RANGEW_COUNT, (double)span, closed, t.container, t.capacity == 0, aq::dev::tag_of<std::remove_cv_t<TT>>::value, sizeof(TT),
+                      nullptr, false, AQG_INT32, 0, t.size, ret);
+}
+template <class S, class TT, template <typename...> class VTT, std::enable_if_t<aq::is_vt<VTT, TT> && std::is_arithmetic_v<S>>* = nullptr>
+inline decayed_t<VTT, uint32_t> countr(S span, const VTT<TT>& t, bool closed = false) { decayed_t<VTT, uint32_t> ret(t.size); countr(span, t, ret, closed); return ret; }
 
 template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>
 inline decayed_t<VT, types::GetFPType<T>> ratios(const VT<T>& arr) { return ratiow(1, arr); }

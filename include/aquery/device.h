@@ -293,6 +293,40 @@ public:
         if (rc != AQG_OK) die("aqg_grouped_decay_from_times_flat", rc, ctx_);
         return vcol_new(c, key, r);
     }
+    // sumr / avgr / minr / maxr / countr of every group's slice (include/aqg.h, time-range windows section): the bounds of a (stamps, span,
+    // frame) are searched ONCE for all groups (aqg_grouped_rangew_bounds_flat) and memoised apart from the folds over them, so that
+    // `sumr(40, t, c)`, `maxr(40, t, c)` and `countr(40, t)` in one loop cost one search and one aqg_rangew_fold each.  vx < 0: COUNT.
+    size_t grouped_rangew_bounds_calls = 0, grouped_rangew_fold_calls = 0;      // calls made so far (the tests count them)
+    int vcol_rangew(GroupCtx* c, int op, int vt, int vx, double span, int frame) {
+        uint64_t sbits;
+        std::memcpy(&sbits, &span, 8);
+        const std::array<uint64_t, 6> bkey{7, sbits, (uint64_t)vt, (uint64_t)frame, 0, 0};
+        int lo;
+        auto bt = c->memo.find(bkey);
+        if (bt != c->memo.end()) lo = bt->second;
+        else {
+            VCol b; b.layout = 1; b.tag = AQG_UINT32;
+            const void* tf = vcol_flat_ptr(c, vt);
+            int rc = aqg_malloc(ctx(), (size_t)c->n * 4 + 16, &b.dptr);
+            if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+            ++grouped_rangew_bounds_calls;
+            rc = aqg_grouped_rangew_bounds_flat(ctx_, c->handle, c->vcols[vt].tag, tf, span, frame, static_cast<uint32_t*>(b.dptr));
+            if (rc != AQG_OK) die("aqg_grouped_rangew_bounds_flat", rc, ctx_);
+            lo = vcol_new(c, bkey, b);
+        }
+        const std::array<uint64_t, 6> key{8, (uint64_t)op, (uint64_t)lo, (uint64_t)(vx + 1), 0, 0};
+        auto it = c->memo.find(key);
+        if (it != c->memo.end()) return it->second;
+        const int xtag = vx < 0 ? (int)AQG_INT32 : c->vcols[vx].tag;
+        VCol r; r.layout = 1; r.tag = aqg_rangew_out_dtype(op, xtag);
+        const void* xf = vx < 0 ? nullptr : vcol_flat_ptr(c, vx);
+        int rc = aqg_malloc(ctx(), (size_t)c->n * esz(r.tag) + 16, &r.dptr);
+        if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+        ++grouped_rangew_fold_calls;
+        rc = aqg_rangew_fold(ctx_, op, xtag, xf, c->n, static_cast<const uint32_t*>(c->vcols[lo].dptr), r.dptr);
+        if (rc != AQG_OK) die("aqg_rangew_fold", rc, ctx_);
+        return vcol_new(c, key, r);
+    }
     // l OP r of two columns of the grouping: in row order when both are (one pass over the whole columns), else in the flat layout
     int vcol_ewise(GroupCtx* c, int op, int l, int r, int ot) {
         const std::array<uint64_t, 6> key{2, (uint64_t)op, (uint64_t)l, (uint64_t)r, (uint64_t)ot, 0};
