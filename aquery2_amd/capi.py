@@ -108,6 +108,17 @@ ASOF_PROTOTYPES = {
                       C.c_int, C.c_void_p],
     "aqg_join_asof_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
 }
+# ctypes prototypes of the window join (applied by load_library)
+WJ_OPEN_LO, WJ_OPEN_HI, WJ_PREVAILING = 1, 2, 4                                         # flags
+WJ_FOLD_STAGED, WJ_FOLD_INPLACE = 16, 32                                                # aqg_join_window_last, beside the ASOF_ROUTE_* bits
+WJ_PROTOTYPES = {
+    "aqg_join_window_bounds": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                               C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "aqg_interval_fold": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "aqg_join_window": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                        C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "aqg_join_window_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 STR_ROUTE_HOST, STR_ROUTE_DEVICE, STR_ROUTE_FALLBACK = 1, 2, 4                          # aqg_str_encode_last
 STR_PROTOTYPES = {
     "aqg_str_encode_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
@@ -146,7 +157,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()) + list(WJ_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -1081,6 +1092,53 @@ class Device:
         """(ASOF_ROUTE_* mask, distinct build tuples, digit passes of the ordering step) of the last join_asof call on this device"""
         r, g, p = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._chk(self.lib.aqg_join_asof_last(self.ctx, C.byref(r), C.byref(g), C.byref(p)), "aqg_join_asof_last")
+        return r.value, g.value, p.value
+
+    # -- window join (include/aqg.h): sides as for join_asof; a window is `before` in front of and `after` behind the probe row's `on`
+    def _wj_sides(self, build_cols, build_on, probe_cols, probe_on):
+        bo, po = self._dev(build_on), self._dev(probe_on)
+        bd, dts, bp = self._keyargs(build_cols) if len(build_cols) else ([], None, None)
+        pd, _, pp = self._keyargs(probe_cols) if len(probe_cols) else ([], None, None)
+        return bo, po, (bd, pd), len(bd), dts, bp, pp
+
+    def join_window_bounds(self, build_cols, build_on, probe_cols, probe_on, before, after, flags=0, keep=False):
+        """(order, lo, hi): the build rows by (group, on, row) and, per probe row, the positions [lo, hi) of that order its window
+        holds (aqg_join_window_bounds); flags: WJ_OPEN_LO | WJ_OPEN_HI | WJ_PREVAILING"""
+        bo, po, held, nk, dts, bp, pp = self._wj_sides(build_cols, build_on, probe_cols, probe_on)
+        order, lo, hi = self.empty(bo.n, np.uint32), self.empty(po.n, np.uint32), self.empty(po.n, np.uint32)
+        self._chk(self.lib.aqg_join_window_bounds(self.ctx, flags, nk, dts, bp, bo.ptr, bo.n, pp, po.ptr, po.n, bo.tag, float(before), float(after),
+                                                  order.ptr, lo.ptr, hi.ptr), "aqg_join_window_bounds")
+        return (order, lo, hi) if keep else (order.to_host(), lo.to_host(), hi.to_host())
+
+    def interval_fold(self, op, x, lo, hi, fill=None, keep=False, out=None):
+        """out[i] = op over x[lo[i] .. min(hi[i], n)); an empty interval gives 0 (COUNT, SUM) or `fill` (None: zero bytes); x may be
+        None for RANGEW_COUNT over a column of `n` = max(hi) rows"""
+        ld = self._dev(np.asarray(lo, np.uint32) if not isinstance(lo, DevBuf) else lo)
+        hd = self._dev(np.asarray(hi, np.uint32) if not isinstance(hi, DevBuf) else hi)
+        xd = self._dev(x) if x is not None else None
+        n = xd.n if xd is not None else 0xFFF00000
+        out = out if out is not None else self.rangew_out(op, xd, ld.n)
+        f = None if fill is None else np.array([fill], dtype=out.dtype)
+        self._chk(self.lib.aqg_interval_fold(self.ctx, op, xd.tag if xd else INT32, xd.ptr if xd else None, n, ld.ptr, hd.ptr, ld.n,
+                                             f.ctypes.data if f is not None else None, out.ptr), "aqg_interval_fold")
+        return out if keep else out.to_host()
+
+    def join_window(self, op, build_cols, build_on, probe_cols, probe_on, before, after, x=None, flags=0, fill=None):
+        """per probe row, `op` (RANGEW_*) over the values `x` of the build rows of its key tuple within `before` in front of and
+        `after` behind its `on` (aqg_join_window); x may be None for RANGEW_COUNT"""
+        bo, po, held, nk, dts, bp, pp = self._wj_sides(build_cols, build_on, probe_cols, probe_on)
+        xd = self._dev(x) if x is not None else None
+        out = self.rangew_out(op, xd, po.n)
+        f = None if fill is None else np.array([fill], dtype=out.dtype)
+        self._chk(self.lib.aqg_join_window(self.ctx, op, flags, nk, dts, bp, bo.ptr, bo.n, pp, po.ptr, po.n, bo.tag, float(before), float(after),
+                                           xd.tag if xd else INT32, xd.ptr if xd else None, f.ctypes.data if f is not None else None, out.ptr),
+                  "aqg_join_window")
+        return out.to_host()
+
+    def join_window_last(self):
+        """(ASOF_ROUTE_* | WJ_FOLD_* mask, distinct build tuples, digit passes of the ordering step) of the last window-join call"""
+        r, g, p = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_join_window_last(self.ctx, C.byref(r), C.byref(g), C.byref(p)), "aqg_join_window_last")
         return r.value, g.value, p.value
 
     def gather_fill(self, x, idx, fill=None):

@@ -59,7 +59,8 @@ struct aqg_ctx {
     struct aqg_groupby* distinct_scratch = nullptr;
     uint32_t join_routes = 0, join_groups = 0, join_slots = 0;   // aqg_join_keys_*: form and route, distinct build tuples and table slots of the last call (aqg_join_last)
     uint32_t asof_routes = 0, asof_groups = 0, asof_passes = 0;   // aqg_join_asof: routes, distinct build tuples and the ordering step's digit passes of the last call (aqg_join_asof_last)
-    uint32_t winq_tile = 0, winq_halo = 0;       // aqg_window_quantiles*: rows per workgroup and halo rows of the last call (aqg_window_quantiles_last)
+    uint32_t wj_routes = 0, wj_groups = 0, wj_passes = 0;         // aqg_join_window* / aqg_interval_fold: the same of the last call, plus the fold's route (aqg_join_window_last)
+    uint32_t winq_tile = 0, winq_halo = 0;      // aqg_window_quantiles*: rows per workgroup and halo rows of the last call (aqg_window_quantiles_last)
     // aqg_rangew*: the packed step counters of the last bounds call (rising steps in the low word, falling in the high one) and the
     // row count of the last fold, from which aqg_rangew_last derives the block tree's geometry
     unsigned long long* rangew_steps = nullptr;

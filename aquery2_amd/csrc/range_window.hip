@@ -6,7 +6,7 @@
 //   bounds   lo[i] by a binary search per row over [slice start, i] on the monotone predicate "d(i, j) within span".  The tile's stamps
 //            and the tile before it are staged in LDS as order-preserving images; a search reads HBM only for the part of its range in
 //            front of that.  The rising / falling steps inside slices are counted in the same launch (one atomic add per workgroup).
-//   fold     a block tree of radix 64 over the layout: level k + 1 holds the fold of every aligned block of 64 elements of level k, and
+//   fold     a block tree of radix 64 over the layout (fold_tree.hpp, shared with the window join): level k + 1 holds the fold of every aligned block of 64 elements of level k, and
 //            levels >= 1 also hold the prefix and suffix folds inside their blocks.  A query [lo, i] is the suffix of lo's block, the
 //            whole blocks between (the same question one level up) and the prefix of i's block.  COMBINING ONLY: nothing is ever
 //            subtracted back out, so a NaN, an Inf or a 1e30 acts on exactly the windows that hold it.  The tree knows nothing of groups:
@@ -19,13 +19,14 @@
 #include "scan_dev.hpp"
 #include "stamps_dev.hpp"
 #include "groupby_handle.hpp"
+#include "fold_tree.hpp"
 
 namespace {
 using namespace aqgscan;
 
-constexpr int RX = 64;                  // radix of the block tree: one wave folds one block
+constexpr int RX = 64;                  // radix of the block tree (fold_tree.hpp), as the staging of the fold kernel below sees it
 constexpr int RSH = 6;
-constexpr int NLV = 5;                  // levels above the rows: 64^5 rows per element of level 5, at most 4 of them
+static_assert(RX == TREE_RX && RSH == TREE_RSH, "the fold kernel walks the tree of fold_tree.hpp");
 
 // ---- bounds --------------------------------------------------------------------------------------------------------------------------
 // order-preserving image of a stamp: uint64 for integer / DATE / TIME columns (d = larger - smaller, exact), the double itself otherwise
@@ -39,7 +40,6 @@ template <class T> struct stamp_img {
         else return (uint64_t)(int64_t)v ^ 0x8000000000000000ull;
     }
 };
-struct span_lim { uint64_t dmax; double span; int closed; };
 template <class I> __device__ inline bool within(I a, I b, const span_lim& s) {
     if constexpr (std::is_same_v<I, double>) { const double d = fabs(a - b); return s.closed ? d <= s.span : d < s.span; }
     else return (a > b ? a - b : b - a) <= s.dmax;
@@ -85,53 +85,7 @@ rangew_bounds_kernel(const T* __restrict__ t, uint32_t n, span_lim lim, const ui
     if (threadIdx.x == 0 && (cnt[0] | cnt[1])) atomicAdd(steps, (unsigned long long)cnt[0] | ((unsigned long long)cnt[1] << 32));
 }
 
-// ---- the block tree ------------------------------------------------------------------------------------------------------------------
-template <class A> struct tree_levels { A* T[NLV + 1]; A* P[NLV + 1]; A* S[NLV + 1]; };      // [1 .. NLV]; level 0 is the column itself
-
-template <class ALG, class A> __device__ inline A wave_prefix(A v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const A y = shfl_up_any(v, o); if (lane >= o) v = ALG::op(y, v); }
-    return v;
-}
-template <class ALG, class A> __device__ inline A wave_suffix(A v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const A y = shfl_idx_any(v, lane + o < 64 ? lane + o : 63); if (lane + o < 64) v = ALG::op(v, y); }
-    return v;
-}
-// One workgroup per 4096 elements of level k (`in`, m of them; RAW: the column, lifted): writes level k + 1 -- the block totals with
-// their prefix and suffix folds -- and its own element of level k + 2.  PS_IN: the prefix / suffix folds of level k as well.
-template <class ALG, class In, bool RAW, bool PS_IN> __global__ void __launch_bounds__(SB)
-rangew_level_kernel(const In* __restrict__ in, uint32_t m, typename ALG::A* __restrict__ Pin, typename ALG::A* __restrict__ Sin,
-                    typename ALG::A* __restrict__ T1, typename ALG::A* __restrict__ P1, typename ALG::A* __restrict__ S1, uint32_t m1,
-                    typename ALG::A* __restrict__ T2) {
-    using A = typename ALG::A;
-    __shared__ A tot[RX];
-    const int lane = lane_id(), wave = wave_id();
-    const uint64_t wg0 = (uint64_t)blockIdx.x * (RX * RX);
-    for (int b = wave; b < RX; b += SB / 64) {
-        const uint64_t idx = wg0 + (uint64_t)b * RX + lane;
-        A v = ALG::identity();
-        if (idx < m) { if constexpr (RAW) v = ALG::lift(in[idx]); else v = in[idx]; }
-        const A pre = wave_prefix<ALG>(v, lane);
-        if constexpr (PS_IN) {
-            const A suf = wave_suffix<ALG>(v, lane);
-            if (idx < m) { Pin[idx] = pre; Sin[idx] = suf; }
-        }
-        if (lane == 63) tot[b] = pre;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const uint64_t idx = (uint64_t)blockIdx.x * RX + lane;
-        const A v = tot[lane];
-        const A pre = wave_prefix<ALG>(v, lane), suf = wave_suffix<ALG>(v, lane);
-        if (idx < m1) { T1[idx] = v; P1[idx] = pre; S1[idx] = suf; }
-        if (lane == 63) T2[blockIdx.x] = pre;
-    }
-}
-
-enum : int { RW_SUM = 0, RW_AVG, RW_MINMAX };
-template <class T, int WR> struct rangew_out { using type = std::conditional_t<WR == RW_AVG, double, std::conditional_t<WR == RW_MINMAX, T, std::conditional_t<std::is_floating_point_v<T>, double, aqg_i128>>>; };
-
+// ---- the fold over the block tree of fold_tree.hpp ---------------------------------------------------------------------------------
 // out[p] = fold of x[min(lo[p], p) .. p].  One workgroup per tile of TS rows; the tile and the tile before it are staged in LDS with
 // their 64 elements of level 1, so a window that begins inside them reads nothing else.
 template <class T, class ALG, int WR> __global__ void __launch_bounds__(SB)
@@ -192,25 +146,6 @@ bool overlaps(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
     return a && b && abytes && bbytes && pa < pb + bbytes && pb < pa + abytes;
 }
 bool stamp_dtype(int t) { return dt_is_num(t) || t == AQG_DATE || t == AQG_TIME; }
-bool good_op(int op) { return op >= AQG_RANGEW_COUNT && op <= AQG_RANGEW_MAX; }
-int out_dtype(int op, int t) {
-    if (!good_op(op)) return AQG_ERROR;
-    if (op == AQG_RANGEW_COUNT) return AQG_UINT32;
-    if (!dt_is_num(t)) return AQG_ERROR;
-    if (op == AQG_RANGEW_SUM) return aqg_long_type(t);
-    return op == AQG_RANGEW_AVG ? AQG_DOUBLE : t;
-}
-
-// span -> the limits of both predicates; AQG_ERR_ARG for a bad frame or span
-int make_lim(aqg_ctx* ctx, double span, int frame, span_lim* lim) {
-    if (frame != AQG_RANGEW_OPEN && frame != AQG_RANGEW_CLOSED) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: bad frame");
-    if (!(frame == AQG_RANGEW_CLOSED ? span >= 0.0 : span > 0.0)) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: span >= 0 (closed) or > 0 (open), not NaN");
-    const double c = frame == AQG_RANGEW_CLOSED ? __builtin_floor(span) : __builtin_ceil(span);
-    uint64_t d = c >= 18446744073709551616.0 ? ~0ull : (uint64_t)c;
-    if (frame == AQG_RANGEW_OPEN && c < 18446744073709551616.0) d -= 1;                 // (c >= 1 here)
-    lim->dmax = d; lim->span = span; lim->closed = frame == AQG_RANGEW_CLOSED;
-    return AQG_OK;
-}
 int check_times(aqg_ctx* ctx, int tt, const void* times, uint32_t n, const void* lo_out, uint64_t out_bytes) {
     if ((!times || !lo_out) && n) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: null column");
     AQG_CHECK_ROWS(ctx, n, "rangew");
@@ -233,14 +168,6 @@ int check_grouped(aqg_ctx* ctx, const aqg_groupby* g) {
     return AQG_OK;
 }
 
-// elements of level k of a column of n rows
-uint32_t level_count(uint32_t n, int k) { uint64_t m = n; for (int j = 0; j < k; ++j) m = (m + RX - 1) / RX; return (uint32_t)m; }
-size_t fold_ws_bytes(uint32_t n) {
-    size_t b = 0;
-    for (int k = 1; k <= NLV; ++k) b += 3 * ((size_t)level_count(n, k) * 16 + 256);
-    return b + 4096;
-}
-
 // g == nullptr: the whole column.  The workspace is the caller's (aqg_flat_gid may reset it: call before any sub-allocation).
 int run_bounds(aqg_ctx* ctx, aqg_groupby* g, int tt, const void* times, uint32_t n, const span_lim& lim, uint32_t* lo_out) {
     const uint32_t *gid = nullptr, *off = nullptr;
@@ -261,25 +188,8 @@ int run_bounds(aqg_ctx* ctx, aqg_groupby* g, int tt, const void* times, uint32_t
 }
 
 template <class T, class ALG, int WR> int run_tree(aqg_ctx* ctx, const T* x, uint32_t n, const uint32_t* lo, void* out) {
-    using A = typename ALG::A;
-    static_assert(sizeof(A) <= 16, "fold_ws_bytes");
-    tree_levels<A> lv{};
-    uint32_t cnt[NLV + 2];
-    for (int k = 0; k <= NLV + 1; ++k) cnt[k] = level_count(n, k);
-    for (int k = 1; k <= NLV; ++k) {
-        AQG_TRY(aqg_ws_get(ctx, (size_t)cnt[k], &lv.T[k]));
-        AQG_TRY(aqg_ws_get(ctx, (size_t)cnt[k], &lv.P[k]));
-        AQG_TRY(aqg_ws_get(ctx, (size_t)cnt[k], &lv.S[k]));
-    }
-    // three launches build levels 1-2, 3-4 and 5 whatever n is (the last one's element of level 6 goes to a spare slot nobody reads)
-    A* spare;
-    AQG_TRY(aqg_ws_get(ctx, (size_t)1, &spare));
-    hipLaunchKernelGGL((rangew_level_kernel<ALG, T, true, false>), dim3(cnt[2]), dim3(SB), 0, ctx->stream, x, n, (A*)nullptr, (A*)nullptr, lv.T[1], lv.P[1], lv.S[1], cnt[1], lv.T[2]);
-    AQG_TRY(aqg_check_launch(ctx, "rangew_level_kernel"));
-    hipLaunchKernelGGL((rangew_level_kernel<ALG, A, false, true>), dim3(cnt[4]), dim3(SB), 0, ctx->stream, (const A*)lv.T[2], cnt[2], lv.P[2], lv.S[2], lv.T[3], lv.P[3], lv.S[3], cnt[3], lv.T[4]);
-    AQG_TRY(aqg_check_launch(ctx, "rangew_level_kernel"));
-    hipLaunchKernelGGL((rangew_level_kernel<ALG, A, false, true>), dim3(cnt[6]), dim3(SB), 0, ctx->stream, (const A*)lv.T[4], cnt[4], lv.P[4], lv.S[4], lv.T[5], lv.P[5], lv.S[5], cnt[5], spare);
-    AQG_TRY(aqg_check_launch(ctx, "rangew_level_kernel"));
+    tree_levels<typename ALG::A> lv{};
+    AQG_TRY((build_tree<T, ALG>(ctx, x, n, lv)));
     aqg_kernel_timer_begin(ctx);
     hipLaunchKernelGGL((rangew_fold_kernel<T, ALG, WR>), dim3(aqg_ceil_div(n, TS)), dim3(SB), 0, ctx->stream, x, n, lo, lv, out);
     aqg_kernel_timer_end(ctx);

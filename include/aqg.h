@@ -667,6 +667,64 @@ int aqg_join_asof(aqg_ctx* ctx, int direction, int flags,
 enum { AQG_ASOF_ROUTE_LDS = 1, AQG_ASOF_ROUTE_HBM = 2, AQG_ASOF_ROUTE_NOKEYS = 4, AQG_ASOF_ROUTE_PRESORTED = 8 };
 int aqg_join_asof_last(aqg_ctx* ctx, uint32_t* routes, uint32_t* build_groups, uint32_t* sort_passes);
 
+/* ---- window join: an aggregate of the build rows in a time window per key tuple (the contract: tests/wj_model.py)
+ * For each probe row, an aggregate over the build rows of the same key tuple whose `on` lies in an interval around the probe row's
+ * own: for each trade the max bid, the average spread, the number of quotes of its symbol in the 5 s before it.  kdb's wj / wj1, an
+ * interval join followed by an aggregate elsewhere; the other half of the time-range windows above, which stay inside one table.
+ * The reference has no counterpart.
+ * KEYS    equality, dtypes, tuple limits and nkeys == 0 exactly as for aqg_join_asof.
+ * `on`    one dtype for both sides, those of aqg_join_asof; anything else AQG_ERR_DTYPE with nothing written.
+ * WINDOW  with B(i) = the build rows whose key tuple equals probe row i's: build row j of B(i) is in the window of probe row i iff
+ *         neither `on` is NaN and b_j == p_i, or b_j < p_i and p_i - b_j is within `before`, or b_j > p_i and b_j - p_i is within
+ *         `after`.  Rows with the probe row's own stamp are therefore always inside.  Windows that do not hold the probe stamp
+ *         (kdb's (t - 5; t - 1)) are out of scope.
+ * DISTANCE  integer `on`: larger minus smaller in unsigned 64-bit arithmetic, never p +- span (nothing wraps at the ends of int64 /
+ *         uint64).  Floating `on`: the one rounded subtraction in double (FLOAT widened first, exactly), which is monotone in b_j.
+ *         -0.0 == +0.0.
+ * WITHIN  a closed side: d <= span, and span >= 0; an open side (AQG_WJ_OPEN_LO for `before`, AQG_WJ_OPEN_HI for `after`): d < span,
+ *         and span > 0.  +Inf is allowed.  NaN, a negative span or unknown flag bits: AQG_ERR_ARG.  For integer `on` each span becomes
+ *         ONE exact limit dmax = floor(span) (closed) or ceil(span) - 1 (open), saturated at 2^64 - 1, as for the time-range windows.
+ * AQG_WJ_PREVAILING (kdb wj, as against wj1): the window additionally holds the one row of B(i) directly in front of it in
+ *         (`on`, row) order -- the as-of BACKWARD partner of the window's start, on ties the highest row id -- even when the window
+ *         is otherwise empty; never for a NaN probe stamp or an absent key.
+ * ORDER   inside a window: ascending (`on`, row id).  It matters for the bracketing of floating sums and for PREVAILING only.
+ * AGGREGATES  the AQG_RANGEW_* enums with the result dtype of aqg_rangew_out_dtype, folded by COMBINING ONLY as above: integer sums
+ *         exact in 128 bits; floating sums a sum of exactly the window's rows with |got - exact| <= m u / (1 - m u) sum |x_j|,
+ *         m = len - 1, u = 2^-53; MIN / MAX an element of the window bit for bit; non-finite rows act on exactly the windows that hold
+ *         them; results are bit-reproducible from call to call.
+ * EMPTY   an empty window: COUNT 0 and SUM 0; AVG / MIN / MAX write *fill_host, an element of the output dtype (NULL: zero bytes --
+ *         the convention of aqg_gather_fill).  nb == 0: every window is empty.  np == 0: nothing written, AQG_OK.
+ * AQG_ERR_ARG: an output overlapping an input, a NULL column with rows, more than AQG_MAX_ROWS rows; every error returns with nothing
+ * written.
+ *   aqg_join_window_bounds  order_out[nb] = the build rows by (group, `on`, row); window i is the positions [lo_i, hi_i) of that order,
+ *                           lo_i == hi_i: empty.  Public so that several aggregates and several value columns share one ordering and
+ *                           one search: a value column materialises with aqg_gather(x, order_out).  First / last of a window are
+ *                           aqg_gather_fill over order[lo] / order[hi - 1] and stay with the caller.  Returns after the stream has
+ *                           drained.
+ *   aqg_interval_fold       out[i] = op over x[lo[i] .. min(hi[i], n)) for m queries over a column of n rows in any layout; it knows
+ *                           nothing of joins, stamps or groups; lo[i] >= hi[i] is the empty interval.  x: the dtypes of
+ *                           aqg_rangew_fold.  Asynchronous on the context's stream, scratch from the context workspace, and the
+ *                           number of launches does not depend on n or m.
+ *   aqg_join_window         bounds + aqg_gather of build_x + fold; returns after the stream has drained, like aqg_join_asof.
+ *   aqg_join_window_last    (diagnostic, like aqg_join_asof_last) the AQG_ASOF_ROUTE_* bits of the last call's search, with
+ *                           AQG_WJ_FOLD_STAGED (the fold copied the column and its level 1 into LDS) or AQG_WJ_FOLD_INPLACE (it read
+ *                           them in place) for the fold; the distinct build tuples; the digit passes of the ordering step.  All zero
+ *                           when nothing ran.                                                                                    */
+enum { AQG_WJ_OPEN_LO = 1, AQG_WJ_OPEN_HI = 2, AQG_WJ_PREVAILING = 4 };   /* flags */
+int aqg_join_window_bounds(aqg_ctx* ctx, int flags, int nkeys, const int* key_dtypes,
+                           const void* const* build_keys, const void* build_on, uint32_t nb,
+                           const void* const* probe_keys, const void* probe_on, uint32_t np,
+                           int on_dtype, double before, double after,
+                           uint32_t* order_out /* [nb] */, uint32_t* lo_out /* [np] */, uint32_t* hi_out /* [np] */);
+int aqg_interval_fold(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, const uint32_t* lo, const uint32_t* hi, uint32_t m,
+                      const void* fill_host, void* out /* [m] */);
+int aqg_join_window(aqg_ctx* ctx, int op, int flags, int nkeys, const int* key_dtypes,
+                    const void* const* build_keys, const void* build_on, uint32_t nb,
+                    const void* const* probe_keys, const void* probe_on, uint32_t np,
+                    int on_dtype, double before, double after, int t, const void* build_x, const void* fill_host, void* out /* [np] */);
+enum { AQG_WJ_FOLD_STAGED = 16, AQG_WJ_FOLD_INPLACE = 32 };
+int aqg_join_window_last(aqg_ctx* ctx, uint32_t* routes, uint32_t* build_groups, uint32_t* sort_passes);
+
 /* ---- the exchange step of row-sharded group-bys -------------------------------------------------
  * Tables shard by row range, one process per GPU; every shard groups its own rows and the shards' group tables are merged
  * by ONE all_gather (RCCL) of a fixed-size payload followed by a re-aggregation.  Because shards are contiguous row
