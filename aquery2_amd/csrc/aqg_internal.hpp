@@ -93,6 +93,12 @@ static inline int aqg_fail(aqg_ctx* ctx, int code, const char* msg) {
 }
 #define AQG_CHECK_ROWS(ctx, n, what) do { if ((uint64_t)(n) > (uint64_t)AQG_MAX_ROWS) return aqg_fail(ctx, AQG_ERR_ARG, what ": more than AQG_MAX_ROWS rows"); } while (0)
 static inline uint32_t aqg_ceil_div(uint32_t n, uint32_t d) { return (uint32_t)(((uint64_t)n + d - 1) / d); }
+// do the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte?  (a null or empty range shares none)
+inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    if (!a || !b || !abytes || !bbytes) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bbytes && y < x + abytes;
+}
 
 // the environment switches of the README (measurement and test aids), read once per process: the tests start a fresh process to force a plan
 struct aqg_switch_set {

@@ -127,31 +127,29 @@ __global__ void __launch_bounds__(256) asof_probe_kernel(AsofArgs a) {
 }
 
 template <class U>
-int asof_run(aqg_ctx* ctx, int forward, int strict, int nkeys, const int* dts, const void* const* bk, const void* build_on, uint32_t nb,
-             const void* const* pk, const void* probe_on, uint32_t np, int kind, int on_dtype, uint32_t* out) {
+int asof_run(aqg_ctx* ctx, const JoinSides& s, int forward, int strict, uint32_t* out) {
     // 1-4. the ordered build side and the groups of the probe rows
     AsofOrder<U> ord(ctx);
-    AQG_TRY(ord.run(ctx, "aqg_join_asof", nkeys, dts, bk, build_on, nb, pk, np, kind, on_dtype));
+    AQG_TRY(ord.run(ctx, "aqg_join_asof", s.nkeys, s.dts, s.bk, s.build_on, s.nb, s.pk, s.np, s.kind, s.on_dtype));
     uint32_t routes = ord.routes;
-    const uint32_t G = ord.G;
     // 5. the search
     AsofArgs a{};
-    a.gid = ord.gid; a.probe_on = probe_on; a.np = np;
-    a.img = ord.img; a.srt = ord.srt; a.off = ord.off; a.nb = nb; a.G = G;
-    a.kind = kind; a.fp = kind == ON_F32 || kind == ON_F64; a.forward = forward; a.upper = forward ? strict : !strict;
-    a.aligned = ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(probe_on) | reinterpret_cast<uintptr_t>(ord.gid)) & 15) == 0;
+    a.gid = ord.gid; a.probe_on = s.probe_on; a.np = s.np;
+    a.img = ord.img; a.srt = ord.srt; a.off = ord.off; a.nb = s.nb; a.G = ord.G;
+    a.kind = s.kind; a.fp = s.kind == ON_F32 || s.kind == ON_F64; a.forward = forward; a.upper = forward ? strict : !strict;
+    a.aligned = ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(s.probe_on) | reinterpret_cast<uintptr_t>(ord.gid)) & 15) == 0;
     a.out = out;
-    const size_t lds = ord.table_bytes(nb);
-    const bool use_lds = join_lds_route(lds, np);
+    const size_t lds = ord.table_bytes(s.nb);
+    const bool use_lds = join_lds_route(lds, s.np);
     routes |= use_lds ? AQG_ASOF_ROUTE_LDS : AQG_ASOF_ROUTE_HBM;
-    const unsigned grid = aqg_grid(ctx, np / AR + 1, 256, 2, use_lds ? (lds <= 20 * 1024 ? 8 : 3) : 8);
+    const unsigned grid = join_probe_grid(ctx, s.np, AR, use_lds, lds);
     aqg_kernel_timer_begin(ctx);
     if (use_lds) hipLaunchKernelGGL((asof_probe_kernel<U, true>), dim3(grid), dim3(256), lds, ctx->stream, a);
     else hipLaunchKernelGGL((asof_probe_kernel<U, false>), dim3(grid), dim3(256), 0, ctx->stream, a);
     aqg_kernel_timer_end(ctx);
     AQG_TRY(aqg_check_launch(ctx, "asof_probe_kernel"));
     ctx->asof_routes = routes;
-    ctx->asof_groups = G;
+    ctx->asof_groups = ord.G;
     ctx->asof_passes = ord.passes;
     return aqg_sync(ctx);                              // the kernels read the handle's and the pool's buffers
 }
@@ -164,27 +162,17 @@ int aqg_join_asof(aqg_ctx* ctx, int direction, int flags, int nkeys, const int* 
                   uint32_t nb, const void* const* probe_keys, const void* probe_on, uint32_t np, int on_dtype, uint32_t* out) {
     if (!ctx) return AQG_ERR_ARG;
     ctx->asof_routes = ctx->asof_groups = ctx->asof_passes = 0;
-    if (nkeys < 0 || nkeys > 8) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_asof: bad argument (0..8 key columns)");
-    if (nkeys) AQG_TRY(aqg_jk_check(ctx, nkeys, key_dtypes, build_keys, nb, probe_keys, np));
-    const int kind = on_kind(on_dtype);
-    if (kind < 0) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_join_asof: the `on` column is INT8/16/32/64, UINT8/16/32/64, FLOAT or DOUBLE");
-    AQG_CHECK_ROWS(ctx, nb, "aqg_join_asof");
-    AQG_CHECK_ROWS(ctx, np, "aqg_join_asof");
-    if ((direction != AQG_ASOF_BACKWARD && direction != AQG_ASOF_FORWARD) || (flags & ~AQG_ASOF_STRICT))
-        return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_asof: bad direction or flags");
-    if ((!build_on && nb) || (!probe_on && np) || (!out && np)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_asof: null column");
-    const size_t ob = (size_t)np * 4, w = (size_t)on_width(kind);
-    bool ov = overlaps(out, ob, build_on, nb * w) || overlaps(out, ob, probe_on, np * w);
-    for (int k = 0; k < nkeys; ++k) {
-        const size_t kw = aqg_dtype_size(key_dtypes[k]);
-        ov = ov || overlaps(out, ob, build_keys[k], nb * kw) || overlaps(out, ob, probe_keys[k], np * kw);
-    }
-    if (ov) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_asof: the output overlaps an input column");
+    JoinSides s;
+    AQG_TRY(check_sides(ctx, "aqg_join_asof", flags, AQG_ASOF_STRICT, nkeys, key_dtypes, build_keys, build_on, nb, probe_keys, probe_on, np, on_dtype, &s));
+    if (direction != AQG_ASOF_BACKWARD && direction != AQG_ASOF_FORWARD) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_asof: bad direction");
+    if (!out && np) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_asof: null column");
+    const size_t ob = (size_t)np * 4;
+    if (over_sides(s, out, ob)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_asof: the output overlaps an input column");
     if (np == 0) return AQG_OK;
     if (nb == 0) { AQG_HIP(ctx, hipMemsetAsync(out, 0xFF, ob, ctx->stream)); return aqg_sync(ctx); }
     const int forward = direction == AQG_ASOF_FORWARD, strict = (flags & AQG_ASOF_STRICT) != 0;
-    if (w == 8) return asof_run<uint64_t>(ctx, forward, strict, nkeys, key_dtypes, build_keys, build_on, nb, probe_keys, probe_on, np, kind, on_dtype, out);
-    return asof_run<uint32_t>(ctx, forward, strict, nkeys, key_dtypes, build_keys, build_on, nb, probe_keys, probe_on, np, kind, on_dtype, out);
+    if (on_width(s.kind) == 8) return asof_run<uint64_t>(ctx, s, forward, strict, out);
+    return asof_run<uint32_t>(ctx, s, forward, strict, out);
 }
 
 int aqg_join_asof_last(aqg_ctx* ctx, uint32_t* routes, uint32_t* build_groups, uint32_t* sort_passes) {

@@ -1,5 +1,5 @@
-// asof_order.hpp -- the ordering step that the as-of join (asof.hip) and the window join (join_window.hip) share: the `on` column's
-// order-preserving images, the build side by (group, on, row), and the groups of the probe rows.
+// asof_order.hpp -- what the as-of join (asof.hip) and the window join (join_window.hip) share: the ordering step (the `on` column's
+// order-preserving images, the build side by (group, on, row), the groups of the probe rows) and the entry checks of the two sides.
 //
 //   group    the build side is grouped on its key tuples (JoinBuild::setup) and the probe side is sent through the tuple probe of
 //            join_keys.hip into gid[np] = {group id | NONE}.  No key columns: one group, no probe.
@@ -109,10 +109,36 @@ struct PoolBuf {
     }
 };
 
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    if (!a || !b || !abytes || !bbytes) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + bbytes && y < x + abytes;
+// ---- the entry checks of both joins -----------------------------------------------------------------------------------------------------
+struct JoinSides {
+    int nkeys; const int* dts; const void* const* bk; const void* build_on; uint32_t nb;
+    const void* const* pk; const void* probe_on; uint32_t np; int kind, on_dtype, flags;
+};
+// The checks of the two sides that the as-of and the window joins share, in the order both have always refused in; `who`: the public
+// entry, `mask`: the flag bits it knows.  s->kind: the OnKind of the `on` column.  (What follows in the callers -- the direction, the
+// spans, the outputs -- refuses with AQG_ERR_ARG like the last two checks here.)
+int check_sides(aqg_ctx* ctx, const char* who, int flags, int mask, int nkeys, const int* dts, const void* const* bk, const void* build_on, uint32_t nb,
+                const void* const* pk, const void* probe_on, uint32_t np, int on_dtype, JoinSides* s) {
+    const std::string w(who);
+    if (nkeys < 0 || nkeys > 8) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": bad argument (0..8 key columns)").c_str());
+    if (nkeys) AQG_TRY(aqg_jk_check(ctx, nkeys, dts, bk, nb, pk, np));
+    const int kind = on_kind(on_dtype);
+    if (kind < 0) return aqg_fail(ctx, AQG_ERR_DTYPE, (w + ": the `on` column is INT8/16/32/64, UINT8/16/32/64, FLOAT or DOUBLE").c_str());
+    if ((uint64_t)nb > (uint64_t)AQG_MAX_ROWS || (uint64_t)np > (uint64_t)AQG_MAX_ROWS) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": more than AQG_MAX_ROWS rows").c_str());
+    if (flags & ~mask) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": unknown flag bits").c_str());
+    if ((!build_on && nb) || (!probe_on && np)) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": null column").c_str());
+    *s = JoinSides{nkeys, dts, bk, build_on, nb, pk, probe_on, np, kind, on_dtype, flags};
+    return AQG_OK;
+}
+// does the output [out, out + bytes) lie over a column of either side?
+bool over_sides(const JoinSides& s, const void* out, size_t bytes) {
+    const size_t w = (size_t)on_width(s.kind);
+    bool ov = overlaps(out, bytes, s.build_on, s.nb * w) || overlaps(out, bytes, s.probe_on, s.np * w);
+    for (int k = 0; k < s.nkeys; ++k) {
+        const size_t kw = aqg_dtype_size(s.dts[k]);
+        ov = ov || overlaps(out, bytes, s.bk[k], s.nb * kw) || overlaps(out, bytes, s.pk[k], s.np * kw);
+    }
+    return ov;
 }
 
 // The ordered build side of one call and the groups of its probe rows.  The object owns the build handle and the pool buffers: it

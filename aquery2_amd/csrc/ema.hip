@@ -106,10 +106,6 @@ int dispatch_ema(aqg_ctx* ctx, const EmaArgs& ea, int t, const void* xv, const u
     });
 }
 
-bool overlaps(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return a && b && pa < pb + bbytes && pb < pa + abytes;
-}
 // the checks every entry shares; fills *ea
 int check_ema(aqg_ctx* ctx, int mode, int t, const void* x, uint32_t n, double alpha, const double* decay, const double* out, EmaArgs* ea) {
     if (mode != AQG_EMA_RECURSIVE && mode != AQG_EMA_ADJUSTED) return aqg_fail(ctx, AQG_ERR_ARG, "ema: bad mode");

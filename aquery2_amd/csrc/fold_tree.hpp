@@ -1,12 +1,15 @@
 // fold_tree.hpp -- the combining-only block tree of radix 64 that the time-range windows (range_window.hip) and the interval fold of
-// the window join (join_window.hip) share, with the span limits and the result types of the AQG_RANGEW_* aggregates.
+// the window join (join_window.hip) share: the span limits and the result types of the AQG_RANGEW_* aggregates, the checks and the
+// op-by-dtype dispatch of a fold (fold_dispatch), the build of the levels and the result store (fold_store).  The walk over the levels
+// stays spelled out in each of the two fold kernels: shared as a device function it cost the time-range fold 1 - 3 %.
 //
 // Level k + 1 holds the fold of every aligned block of 64 elements of level k, and levels >= 1 also hold the prefix and suffix folds
 // inside their blocks.  A range [a, b] is the suffix of a's block, the whole blocks between (the same question one level up) and the
 // prefix of b's block.  COMBINING ONLY: nothing is ever subtracted back out.  Level 0 keeps no prefix / suffix folds: they would cost
 // 2 sizeof(A) bytes per row written and read back (32 for 64-bit sums) against at most 63 reads at either end of a range; the levels
 // above cost 3 sizeof(A) / 63 bytes per row all together.  No atomics and no look-back: the bracketing of a floating sum depends on n
-// and the two ends alone.
+// and the two ends alone (and on the kernel: range_window.hip folds staged whole blocks directly, join_window.hip always walks up;
+// tests/golden/fold_digests.json pins the bits of both).
 #pragma once
 #include "aqg_internal.hpp"
 #include "dev_common.hpp"
@@ -47,9 +50,50 @@ int out_dtype(int op, int t) {
 enum : int { RW_SUM = 0, RW_AVG, RW_MINMAX };
 template <class T, int WR> struct rangew_out { using type = std::conditional_t<WR == RW_AVG, double, std::conditional_t<WR == RW_MINMAX, T, std::conditional_t<std::is_floating_point_v<T>, double, aqg_i128>>>; };
 
+// The checks of a fold's op, dtype and value column x[0 .. n).  `rangew`: the entries of range_window.hip, whose output has n elements
+// as well and is checked here too; each family refuses in the order it always has (errors of several kinds at once are tested).
+int check_fold(aqg_ctx* ctx, const char* who, int op, int t, const void* x, uint32_t n, bool rangew = false, const void* out = nullptr) {
+    const std::string w(who);
+    const bool val = op != AQG_RANGEW_COUNT;
+    if (!good_op(op)) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": bad op").c_str());
+    if (rangew) {
+        if ((!out || (!x && val)) && n) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": null column").c_str());
+        if ((uint64_t)n > (uint64_t)AQG_MAX_ROWS) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": more than AQG_MAX_ROWS rows").c_str());
+    }
+    if (val && !dt_is_num(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, (w + (rangew ? ": the column dtype is not numeric" : ": the value column's dtype is not numeric")).c_str());
+    if (!rangew && val && !x && n) return aqg_fail(ctx, AQG_ERR_ARG, (w + ": null column").c_str());
+    if (rangew && val && overlaps(out, (size_t)n * dt_size(out_dtype(op, t)), x, (size_t)n * dt_size(t)))
+        return aqg_fail(ctx, AQG_ERR_ARG, (w + ": out overlaps an input").c_str());
+    return AQG_OK;
+}
+
+// the one switch over the aggregates that fold (not COUNT) by numeric dtype: fn.template operator()<T, ALG, WR>()
+template <class F> int fold_dispatch(int op, int t, F&& fn) {
+    return aqg_dispatch_num(t, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        switch (op) {
+        case AQG_RANGEW_SUM: return fn.template operator()<T, sum_alg<T>, RW_SUM>();
+        case AQG_RANGEW_AVG: return fn.template operator()<T, sum_alg<T>, RW_AVG>();
+        case AQG_RANGEW_MIN: return fn.template operator()<T, min_alg<T>, RW_MINMAX>();
+        case AQG_RANGEW_MAX: return fn.template operator()<T, max_alg<T>, RW_MINMAX>();
+        }
+        return AQG_ERR_ARG;
+    });
+}
+
 // ---- the block tree ------------------------------------------------------------------------------------------------------------------
 template <class A> struct tree_levels { A* T[NLV + 1]; A* P[NLV + 1]; A* S[NLV + 1]; };      // [1 .. NLV]; level 0 is the column itself
 
+// ---- the result store ---------------------------------------------------------------------------------------------------------------
+// out[i] = the result of `op` from the accumulator of a range of `len` rows
+template <class T, int WR, class A> __device__ inline void fold_store(typename rangew_out<T, WR>::type* __restrict__ out, uint64_t i, const A& acc, uint32_t len) {
+    if constexpr (WR == RW_MINMAX) out[i] = acc;
+    else if constexpr (WR == RW_AVG) out[i] = sum_alg<T>::to_double(acc) / (double)len;
+    else if constexpr (std::is_floating_point_v<T>) out[i] = acc;
+    else out[i] = sum_alg<T>::to_i128(acc);                               // (one 16-byte store)
+}
+
+// ---- the build -------------------------------------------------------------------------------------------------------------------------
 template <class ALG, class A> __device__ inline A wave_prefix(A v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const A y = shfl_up_any(v, o); if (lane >= o) v = ALG::op(y, v); }

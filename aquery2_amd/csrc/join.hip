@@ -156,11 +156,9 @@ size_t table_bytes(uint32_t n) { return (size_t)pow2_at_least((uint64_t)n * 2) *
 bool launch_probe(aqg_ctx* ctx, int t, const void* pk, uint32_t np, const JTable& jt, uint32_t* out) {
     const size_t lds = (size_t)jt.cap * 12;
     const bool use_lds = join_lds_route(lds, np);
-    if (use_lds) {
-        hipLaunchKernelGGL((jt_probe_kernel<true>), dim3(aqg_grid(ctx, np / 4 + 1, 256, 2, lds <= 20 * 1024 ? 8 : 3)), dim3(256), lds, ctx->stream, t, pk, np, jt, out);
-    } else {
-        hipLaunchKernelGGL((jt_probe_kernel<false>), dim3(aqg_grid(ctx, np / 4 + 1, 256, 2, 8)), dim3(256), 0, ctx->stream, t, pk, np, jt, out);
-    }
+    const unsigned grid = join_probe_grid(ctx, np, 4, use_lds, lds);
+    if (use_lds) hipLaunchKernelGGL((jt_probe_kernel<true>), dim3(grid), dim3(256), lds, ctx->stream, t, pk, np, jt, out);
+    else hipLaunchKernelGGL((jt_probe_kernel<false>), dim3(grid), dim3(256), 0, ctx->stream, t, pk, np, jt, out);
     return use_lds;
 }
 

@@ -199,7 +199,7 @@ int launch_probe(aqg_ctx* ctx, const JKCols& kp, uint32_t np, const JKTable& t, 
     ctx->join_routes = (kp.packed ? AQG_JOIN_ROUTE_PACKED : AQG_JOIN_ROUTE_WIDE) | (use_lds ? AQG_JOIN_ROUTE_LDS : AQG_JOIN_ROUTE_HBM);
     ctx->join_groups = t.G;
     ctx->join_slots = t.cap;
-    const unsigned grid = aqg_grid(ctx, np / JR + 1, 256, 2, use_lds ? (lds <= 20 * 1024 ? 8 : 3) : 8);
+    const unsigned grid = join_probe_grid(ctx, np, JR, use_lds, lds);
     const size_t sh = use_lds ? lds : 0;
 #define JK_LAUNCH(P, L) hipLaunchKernelGGL((jk_probe_kernel<P, L>), dim3(grid), dim3(256), sh, ctx->stream, kp, np, t, remap, out, aligned)
     if (kp.packed) { if (use_lds) JK_LAUNCH(true, true); else JK_LAUNCH(true, false); }

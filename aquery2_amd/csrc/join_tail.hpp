@@ -11,6 +11,11 @@ inline uint32_t pow2_at_least(uint64_t v) { uint64_t p = 16; while (p < v) p <<=
 constexpr size_t JOIN_LDS_LIMIT = 48 * 1024;
 constexpr uint32_t JOIN_LDS_MIN_ROWS = 1u << 16;
 inline bool join_lds_route(size_t table_bytes, uint32_t np) { return table_bytes <= JOIN_LDS_LIMIT && np >= JOIN_LDS_MIN_ROWS; }
+// The grid of a probe kernel of 256 threads with `rows_per_lane` consecutive probe rows per lane, two such chunks per thread: 8
+// workgroups per CU reading in place or with up to 20 KB of LDS each, 3 with more (`lds`: the bytes the LDS route stages).
+inline unsigned join_probe_grid(const aqg_ctx* ctx, uint32_t np, int rows_per_lane, bool use_lds, size_t lds) {
+    return aqg_grid(ctx, np / rows_per_lane + 1, 256, 2, use_lds ? (lds <= 20 * 1024 ? 8 : 3) : 8);
+}
 
 // The grouped build side of one call: the handle and the device buffers a join holds until it returns, freed in the destructor.
 struct JoinBuild {

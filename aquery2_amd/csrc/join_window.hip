@@ -209,10 +209,7 @@ interval_fold_kernel(const T* __restrict__ x, uint32_t n, const uint32_t* __rest
             }
         }
         const A acc = ALG::op(ALG::op(left, mid), right);
-        if constexpr (WR == RW_MINMAX) out[i] = acc;
-        else if constexpr (WR == RW_AVG) out[i] = sum_alg<T>::to_double(acc) / (double)len;
-        else if constexpr (std::is_floating_point_v<T>) out[i] = acc;
-        else out[i] = sum_alg<T>::to_i128(acc);                           // (one 16-byte store)
+        fold_store<T, WR>(out, i, acc, len);
     }
 }
 __global__ void __launch_bounds__(256) interval_count_kernel(uint32_t n, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, uint32_t m,
@@ -281,50 +278,19 @@ int fold_run(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, const uint
     }
     AQG_TRY(aqg_ws_reset(ctx));
     AQG_TRY(aqg_ws_ensure(ctx, fold_ws_bytes(n)));
-    return aqg_dispatch_num(t, [&](auto tag) -> int {
-        using T = typename decltype(tag)::type;
-        const T* x = static_cast<const T*>(xv);
-        switch (op) {
-        case AQG_RANGEW_SUM: return fold_tree_run<T, sum_alg<T>, RW_SUM>(ctx, x, n, lo, hi, m, fill, out, route);
-        case AQG_RANGEW_AVG: return fold_tree_run<T, sum_alg<T>, RW_AVG>(ctx, x, n, lo, hi, m, fill, out, route);
-        case AQG_RANGEW_MIN: return fold_tree_run<T, min_alg<T>, RW_MINMAX>(ctx, x, n, lo, hi, m, fill, out, route);
-        case AQG_RANGEW_MAX: return fold_tree_run<T, max_alg<T>, RW_MINMAX>(ctx, x, n, lo, hi, m, fill, out, route);
-        }
-        return AQG_ERR_ARG;
+    return fold_dispatch(op, t, [&]<class T, class ALG, int WR>() -> int {
+        return fold_tree_run<T, ALG, WR>(ctx, static_cast<const T*>(xv), n, lo, hi, m, fill, out, route);
     });
 }
 
-struct WjSides {
-    int nkeys; const int* dts; const void* const* bk; const void* build_on; uint32_t nb;
-    const void* const* pk; const void* probe_on; uint32_t np; int kind, on_dtype, flags; span_lim before, after;
-};
+struct WjSides : JoinSides { span_lim before, after; };
 
-// the checks the three join entries share; *kind_out: the OnKind of the `on` column
-int check_sides(aqg_ctx* ctx, int flags, int nkeys, const int* dts, const void* const* bk, const void* build_on, uint32_t nb, const void* const* pk,
-                const void* probe_on, uint32_t np, int on_dtype, double before, double after, WjSides* s) {
-    if (nkeys < 0 || nkeys > 8) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_window: bad argument (0..8 key columns)");
-    if (nkeys) AQG_TRY(aqg_jk_check(ctx, nkeys, dts, bk, nb, pk, np));
-    const int kind = on_kind(on_dtype);
-    if (kind < 0) return aqg_fail(ctx, AQG_ERR_DTYPE, "aqg_join_window: the `on` column is INT8/16/32/64, UINT8/16/32/64, FLOAT or DOUBLE");
-    AQG_CHECK_ROWS(ctx, nb, "aqg_join_window");
-    AQG_CHECK_ROWS(ctx, np, "aqg_join_window");
-    if (flags & ~WJ_FLAGS) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_window: unknown flag bits");
-    span_lim lb, la;
-    AQG_TRY(make_lim(ctx, before, (flags & AQG_WJ_OPEN_LO) ? AQG_RANGEW_OPEN : AQG_RANGEW_CLOSED, &lb, "aqg_join_window (before)"));
-    AQG_TRY(make_lim(ctx, after, (flags & AQG_WJ_OPEN_HI) ? AQG_RANGEW_OPEN : AQG_RANGEW_CLOSED, &la, "aqg_join_window (after)"));
-    if ((!build_on && nb) || (!probe_on && np)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_window: null column");
-    *s = WjSides{nkeys, dts, bk, build_on, nb, pk, probe_on, np, kind, on_dtype, flags, lb, la};
-    return AQG_OK;
-}
-// does the output [out, out + bytes) lie over a column of either side?
-bool over_sides(const WjSides& s, const void* out, size_t bytes) {
-    const size_t w = (size_t)on_width(s.kind);
-    bool ov = overlaps(out, bytes, s.build_on, s.nb * w) || overlaps(out, bytes, s.probe_on, s.np * w);
-    for (int k = 0; k < s.nkeys; ++k) {
-        const size_t kw = aqg_dtype_size(s.dts[k]);
-        ov = ov || overlaps(out, bytes, s.bk[k], s.nb * kw) || overlaps(out, bytes, s.pk[k], s.np * kw);
-    }
-    return ov;
+// the checks the three join entries share (asof_order.hpp's of the two sides, then the spans)
+int check_wj_sides(aqg_ctx* ctx, int flags, int nkeys, const int* dts, const void* const* bk, const void* build_on, uint32_t nb, const void* const* pk,
+                   const void* probe_on, uint32_t np, int on_dtype, double before, double after, WjSides* s) {
+    AQG_TRY(check_sides(ctx, "aqg_join_window", flags, WJ_FLAGS, nkeys, dts, bk, build_on, nb, pk, probe_on, np, on_dtype, s));
+    AQG_TRY(make_lim(ctx, before, (flags & AQG_WJ_OPEN_LO) ? AQG_RANGEW_OPEN : AQG_RANGEW_CLOSED, &s->before, "aqg_join_window (before)"));
+    return make_lim(ctx, after, (flags & AQG_WJ_OPEN_HI) ? AQG_RANGEW_OPEN : AQG_RANGEW_CLOSED, &s->after, "aqg_join_window (after)");
 }
 
 // order (into order_out), then lo / hi of every probe row; nb, np > 0.  Queued on the stream: the caller keeps `ord` until it drained.
@@ -349,7 +315,7 @@ int bounds_run(aqg_ctx* ctx, AsofOrder<U>& ord, const WjSides& s, uint32_t* orde
     const size_t table = ord.table_bytes(s.nb);        // the as-of join's table bytes decide the route; the rows are not staged here
     const bool use_lds = join_lds_route(table, s.np);
     const size_t lds = (size_t)s.nb * sizeof(U) + ((size_t)ord.G + 1) * 4;
-    const unsigned grid = aqg_grid(ctx, s.np / AR + 1, 256, 2, use_lds ? (lds <= 20 * 1024 ? 8 : 3) : 8);
+    const unsigned grid = join_probe_grid(ctx, s.np, AR, use_lds, lds);
     aqg_kernel_timer_begin(ctx);
     if (use_lds) hipLaunchKernelGGL((wj_bounds_kernel<U, true>), dim3(grid), dim3(256), lds, ctx->stream, a);
     else hipLaunchKernelGGL((wj_bounds_kernel<U, false>), dim3(grid), dim3(256), 0, ctx->stream, a);
@@ -390,13 +356,6 @@ int window_call(aqg_ctx* ctx, const WjSides& s, int op, int t, const void* build
     return AQG_OK;
 }
 
-int check_fold_args(aqg_ctx* ctx, const char* who, int op, int t, const void* x, uint32_t n) {
-    if (!good_op(op)) return aqg_fail(ctx, AQG_ERR_ARG, (std::string(who) + ": bad op").c_str());
-    if (op != AQG_RANGEW_COUNT && !dt_is_num(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, (std::string(who) + ": the value column's dtype is not numeric").c_str());
-    if (op != AQG_RANGEW_COUNT && !x && n) return aqg_fail(ctx, AQG_ERR_ARG, (std::string(who) + ": null column").c_str());
-    return AQG_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -407,7 +366,7 @@ int aqg_join_window_bounds(aqg_ctx* ctx, int flags, int nkeys, const int* key_dt
     if (!ctx) return AQG_ERR_ARG;
     wj_clear(ctx);
     WjSides s;
-    AQG_TRY(check_sides(ctx, flags, nkeys, key_dtypes, build_keys, build_on, nb, probe_keys, probe_on, np, on_dtype, before, after, &s));
+    AQG_TRY(check_wj_sides(ctx, flags, nkeys, key_dtypes, build_keys, build_on, nb, probe_keys, probe_on, np, on_dtype, before, after, &s));
     if ((!order_out && nb) || ((!lo_out || !hi_out) && np)) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_window_bounds: null output");
     const size_t ob = (size_t)nb * 4, pb = (size_t)np * 4;
     if (over_sides(s, order_out, ob) || over_sides(s, lo_out, pb) || over_sides(s, hi_out, pb) || overlaps(order_out, ob, lo_out, pb) ||
@@ -427,7 +386,7 @@ int aqg_interval_fold(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, co
                       const void* fill_host, void* out) {
     if (!ctx) return AQG_ERR_ARG;
     wj_clear(ctx);
-    AQG_TRY(check_fold_args(ctx, "aqg_interval_fold", op, t, x, n));
+    AQG_TRY(check_fold(ctx, "aqg_interval_fold", op, t, x, n));
     AQG_CHECK_ROWS(ctx, n, "aqg_interval_fold");
     AQG_CHECK_ROWS(ctx, m, "aqg_interval_fold");
     if ((!lo || !hi || !out) && m) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_interval_fold: null column");
@@ -447,8 +406,8 @@ int aqg_join_window(aqg_ctx* ctx, int op, int flags, int nkeys, const int* key_d
     if (!ctx) return AQG_ERR_ARG;
     wj_clear(ctx);
     WjSides s;
-    AQG_TRY(check_fold_args(ctx, "aqg_join_window", op, t, build_x, nb));
-    AQG_TRY(check_sides(ctx, flags, nkeys, key_dtypes, build_keys, build_on, nb, probe_keys, probe_on, np, on_dtype, before, after, &s));
+    AQG_TRY(check_fold(ctx, "aqg_join_window", op, t, build_x, nb));
+    AQG_TRY(check_wj_sides(ctx, flags, nkeys, key_dtypes, build_keys, build_on, nb, probe_keys, probe_on, np, on_dtype, before, after, &s));
     if (!out && np) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_join_window: null output");
     const int odt = out_dtype(op, t);
     const size_t ob = (size_t)np * dt_size(odt);

@@ -6,11 +6,14 @@
 //   bounds   lo[i] by a binary search per row over [slice start, i] on the monotone predicate "d(i, j) within span".  The tile's stamps
 //            and the tile before it are staged in LDS as order-preserving images; a search reads HBM only for the part of its range in
 //            front of that.  The rising / falling steps inside slices are counted in the same launch (one atomic add per workgroup).
-//   fold     a block tree of radix 64 over the layout (fold_tree.hpp, shared with the window join): level k + 1 holds the fold of every aligned block of 64 elements of level k, and
-//            levels >= 1 also hold the prefix and suffix folds inside their blocks.  A query [lo, i] is the suffix of lo's block, the
-//            whole blocks between (the same question one level up) and the prefix of i's block.  COMBINING ONLY: nothing is ever
-//            subtracted back out, so a NaN, an Inf or a 1e30 acts on exactly the windows that hold it.  The tree knows nothing of groups:
-//            lo >= the slice start, so a block that straddles a group start is only ever entered through the part inside the window.
+//   fold     a block tree of radix 64 over the layout (fold_tree.hpp, shared with the window join: the tree, its build, the result
+//            store, the op-by-dtype dispatch and the fold's argument checks): level k + 1 holds the fold of every aligned block of 64
+//            elements of level k, and levels >= 1 also hold the prefix and suffix folds inside their blocks.  A query [lo, i] is the
+//            suffix of lo's block, the whole blocks between (the same question one level up) and the prefix of i's block.  Whole
+//            blocks that all lie in the staged level 1 are folded directly, in one loop: the window join's fold never does that, so
+//            the two bracket a floating sum differently, on purpose.  COMBINING ONLY: nothing is ever subtracted back out, so a NaN,
+//            an Inf or a 1e30 acts on exactly the windows that hold it.  The tree knows nothing of groups: lo >= the slice start, so
+//            a block that straddles a group start is only ever entered through the part inside the window.
 // Level 0 keeps no prefix / suffix folds: they would cost 2 sizeof(A) bytes per row written and read back (32 for 64-bit sums) against
 // at most 63 LDS reads at either end of a window; the levels above cost 3 sizeof(A) / 63 bytes per row all together.
 // No atomics and no look-back in the fold: the bracketing of a floating sum depends on n, lo and i alone.
@@ -24,7 +27,7 @@
 namespace {
 using namespace aqgscan;
 
-constexpr int RX = 64;                  // radix of the block tree (fold_tree.hpp), as the staging of the fold kernel below sees it
+constexpr int RX = 64;                  // radix of the block tree (fold_tree.hpp), as the fold kernel below sees it; tests/timewin_cases.py reads it
 constexpr int RSH = 6;
 static_assert(RX == TREE_RX && RSH == TREE_RSH, "the fold kernel walks the tree of fold_tree.hpp");
 
@@ -129,10 +132,7 @@ rangew_fold_kernel(const T* __restrict__ x, uint32_t n, const uint32_t* __restri
             }
         }
         const A acc = ALG::op(ALG::op(left, mid), right);
-        if constexpr (WR == RW_MINMAX) out[p] = acc;
-        else if constexpr (WR == RW_AVG) out[p] = sum_alg<T>::to_double(acc) / (double)len;
-        else if constexpr (std::is_floating_point_v<T>) out[p] = acc;
-        else out[p] = sum_alg<T>::to_i128(acc);
+        fold_store<T, WR>(out, p, acc, len);
     }
 }
 __global__ void __launch_bounds__(SB) rangew_count_kernel(uint32_t n, const uint32_t* __restrict__ lo, uint32_t* __restrict__ out) {
@@ -141,25 +141,12 @@ __global__ void __launch_bounds__(SB) rangew_count_kernel(uint32_t n, const uint
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-bool overlaps(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return a && b && abytes && bbytes && pa < pb + bbytes && pb < pa + abytes;
-}
 bool stamp_dtype(int t) { return dt_is_num(t) || t == AQG_DATE || t == AQG_TIME; }
 int check_times(aqg_ctx* ctx, int tt, const void* times, uint32_t n, const void* lo_out, uint64_t out_bytes) {
     if ((!times || !lo_out) && n) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: null column");
     AQG_CHECK_ROWS(ctx, n, "rangew");
     if (!stamp_dtype(tt)) return aqg_fail(ctx, AQG_ERR_DTYPE, "rangew: numeric, DATE and TIME stamps");
     if (overlaps(lo_out, out_bytes, times, (uint64_t)n * dt_size(tt))) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: out overlaps the stamps");
-    return AQG_OK;
-}
-int check_fold(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, const void* out) {
-    if (!good_op(op)) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: bad op");
-    if ((!out || (!x && op != AQG_RANGEW_COUNT)) && n) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: null column");
-    AQG_CHECK_ROWS(ctx, n, "rangew");
-    if (op != AQG_RANGEW_COUNT && !dt_is_num(t)) return aqg_fail(ctx, AQG_ERR_DTYPE, "rangew: the column dtype is not numeric");
-    if (op != AQG_RANGEW_COUNT && overlaps(out, (uint64_t)n * dt_size(out_dtype(op, t)), x, (uint64_t)n * dt_size(t)))
-        return aqg_fail(ctx, AQG_ERR_ARG, "rangew: out overlaps an input");
     return AQG_OK;
 }
 int check_grouped(aqg_ctx* ctx, const aqg_groupby* g) {
@@ -202,17 +189,7 @@ int run_fold(aqg_ctx* ctx, int op, int t, const void* xv, uint32_t n, const uint
         hipLaunchKernelGGL(rangew_count_kernel, dim3(aqg_ceil_div(n, SB)), dim3(SB), 0, ctx->stream, n, lo, static_cast<uint32_t*>(out));
         return aqg_check_launch(ctx, "rangew_count_kernel");
     }
-    return aqg_dispatch_num(t, [&](auto tag) -> int {
-        using T = typename decltype(tag)::type;
-        const T* x = static_cast<const T*>(xv);
-        switch (op) {
-        case AQG_RANGEW_SUM: return run_tree<T, sum_alg<T>, RW_SUM>(ctx, x, n, lo, out);
-        case AQG_RANGEW_AVG: return run_tree<T, sum_alg<T>, RW_AVG>(ctx, x, n, lo, out);
-        case AQG_RANGEW_MIN: return run_tree<T, min_alg<T>, RW_MINMAX>(ctx, x, n, lo, out);
-        case AQG_RANGEW_MAX: return run_tree<T, max_alg<T>, RW_MINMAX>(ctx, x, n, lo, out);
-        }
-        return AQG_ERR_ARG;
-    });
+    return fold_dispatch(op, t, [&]<class T, class ALG, int WR>() -> int { return run_tree<T, ALG, WR>(ctx, static_cast<const T*>(xv), n, lo, out); });
 }
 uint64_t out_bytes(int op, int t, uint32_t n) { return (uint64_t)n * dt_size(out_dtype(op, t)); }
 
@@ -250,7 +227,7 @@ int aqg_grouped_rangew_bounds_flat(aqg_ctx* ctx, aqg_groupby* g, int tt, const v
 
 int aqg_rangew_fold(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, const uint32_t* lo, void* out) {
     if (!ctx) return AQG_ERR_ARG;
-    AQG_TRY(check_fold(ctx, op, t, x, n, out));
+    AQG_TRY(check_fold(ctx, "rangew", op, t, x, n, true, out));
     if (!lo && n) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: null bounds");
     if (overlaps(out, out_bytes(op, t, n), lo, (uint64_t)n * 4)) return aqg_fail(ctx, AQG_ERR_ARG, "rangew: out overlaps the bounds");
     if (n == 0) return AQG_OK;
@@ -262,7 +239,7 @@ int aqg_rangew_fold(aqg_ctx* ctx, int op, int t, const void* x, uint32_t n, cons
 int aqg_rangew(aqg_ctx* ctx, int op, int tt, const void* times, double span, int frame, int t, const void* x, uint32_t n, void* out) {
     if (!ctx) return AQG_ERR_ARG;
     span_lim lim;
-    AQG_TRY(check_fold(ctx, op, t, x, n, out));
+    AQG_TRY(check_fold(ctx, "rangew", op, t, x, n, true, out));
     AQG_TRY(make_lim(ctx, span, frame, &lim));
     AQG_TRY(check_times(ctx, tt, times, n, out, out_bytes(op, t, n)));
     if (n == 0) return AQG_OK;
@@ -275,7 +252,7 @@ int aqg_grouped_rangew_flat(aqg_ctx* ctx, aqg_groupby* g, int op, int tt, const 
     AQG_TRY(check_grouped(ctx, g));
     span_lim lim;
     const uint32_t n = g->n;
-    AQG_TRY(check_fold(ctx, op, t, xflat, n, out_flat));
+    AQG_TRY(check_fold(ctx, "rangew", op, t, xflat, n, true, out_flat));
     AQG_TRY(make_lim(ctx, span, frame, &lim));
     AQG_TRY(check_times(ctx, tt, times_flat, n, out_flat, out_bytes(op, t, n)));
     if (n == 0 || g->ngroups == 0) return AQG_OK;
@@ -290,7 +267,7 @@ int aqg_grouped_rangew(aqg_ctx* ctx, aqg_groupby* g, int op, int tt, const void*
     AQG_TRY(check_grouped(ctx, g));
     span_lim lim;
     const uint32_t n = g->n;
-    AQG_TRY(check_fold(ctx, op, t, x_row, n, out_flat));
+    AQG_TRY(check_fold(ctx, "rangew", op, t, x_row, n, true, out_flat));
     AQG_TRY(make_lim(ctx, span, frame, &lim));
     AQG_TRY(check_times(ctx, tt, times_row, n, out_flat, out_bytes(op, t, n)));
     if (n == 0 || g->ngroups == 0) return AQG_OK;
