@@ -7,3 +7,5 @@ used by tests/ and bench.py; it contains no compute of its own and no CPU fallba
 """
 from . import capi  # noqa: F401
 from .capi import Device, DevBuf, AqgError, Comm, ThreadRanks, lib_path, load_library  # noqa: F401
+from .capi import (RANK_MIN, RANK_MAX, RANK_DENSE, RANK_FIRST, RANK_AVERAGE, RANK_PERCENT, RANK_CUME_DIST, RANK_NTILE,  # noqa: F401
+                   RANK_ROUTE_SMALL, RANK_ROUTE_SORTED)

@@ -58,6 +58,16 @@ WINQ_PROTOTYPES = {
     "aqg_grouped_window_quantiles_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
     "aqg_window_quantiles_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
 }
+# ctypes prototypes of the ranking entries (applied by load_library); RANK_*: aqg_rank's methods, RANK_ROUTE_*: aqg_rank_last
+RANK_MIN, RANK_MAX, RANK_DENSE, RANK_FIRST, RANK_AVERAGE, RANK_PERCENT, RANK_CUME_DIST, RANK_NTILE = range(8)
+RANK_ROUTE_SMALL, RANK_ROUTE_SORTED = 1, 2
+RANK_PROTOTYPES = {
+    "aqg_rank_out_dtype": [C.c_int],
+    "aqg_rank": [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_grouped_rank": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_grouped_rank_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
+    "aqg_rank_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 # ctypes prototypes of the exponential moving averages (applied by load_library)
 EMA_RECURSIVE, EMA_ADJUSTED = 0, 1
 EMA_PROTOTYPES = {
@@ -157,7 +167,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()) + list(WJ_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(RANK_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()) + list(WJ_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -773,6 +783,34 @@ class Device:
         t, h = C.c_uint32(), C.c_uint32()
         self._chk(self.lib.aqg_window_quantiles_last(self.ctx, C.byref(t), C.byref(h)), "aqg_window_quantiles_last")
         return t.value, h.value
+
+    # -- ranking (comparison counting in LDS / stable sort + one rank-emit pass: include/aqg.h, ranking section)
+    def rank_out(self, method, n):
+        """the device column a rank call of `method` over n rows writes: uint32, or float64 for RANK_AVERAGE / PERCENT / CUME_DIST"""
+        tag = self.lib.aqg_rank_out_dtype(method)
+        return self.empty(n, TAG2NP[tag] if tag >= 0 else np.uint32)
+
+    def rank(self, x, method, order=ORDER_ASC, k=0, keep=False, out=None):
+        """where every row stands in the whole column, 1-based: RANK_MIN / MAX / DENSE / FIRST / NTILE (k buckets) as uint32,
+        RANK_AVERAGE / PERCENT / CUME_DIST as float64; ties and NaNs as aqg_sort_rows orders them"""
+        xd = self._dev(x)
+        out = out if out is not None else self.rank_out(method, xd.n)
+        self._chk(self.lib.aqg_rank(self.ctx, method, order, k, xd.tag, xd.ptr, xd.n, out.ptr), "aqg_rank")
+        return out if keep else out.to_host()
+
+    def grouped_rank(self, gb, x, method, order=ORDER_ASC, k=0, flat=False, keep=False, out=None):
+        """rank within every group of a build, n values in the flat layout: `x` in row layout, or (flat=True) already in the flat layout"""
+        xd = self._dev(x)
+        out = out if out is not None else self.rank_out(method, xd.n)
+        fn = self.lib.aqg_grouped_rank_flat if flat else self.lib.aqg_grouped_rank
+        self._chk(fn(self.ctx, gb.h, method, order, k, xd.tag, xd.ptr, out.ptr), "aqg_grouped_rank")
+        return out if keep else out.to_host()
+
+    def rank_last(self):
+        """(mask of RANK_ROUTE_* the last rank call took, sorted entries one workgroup of its emit kernel owns)"""
+        r, t = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_rank_last(self.ctx, C.byref(r), C.byref(t)), "aqg_rank_last")
+        return r.value, t.value
 
     # -- exponential moving averages (ordered scan of affine maps: include/aqg.h, exponential moving averages section)
     def ema(self, x, alpha=None, decay=None, mode=EMA_RECURSIVE, keep=False, out=None):

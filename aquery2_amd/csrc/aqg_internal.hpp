@@ -60,6 +60,7 @@ struct aqg_ctx {
     uint32_t join_routes = 0, join_groups = 0, join_slots = 0;   // aqg_join_keys_*: form and route, distinct build tuples and table slots of the last call (aqg_join_last)
     uint32_t asof_routes = 0, asof_groups = 0, asof_passes = 0;   // aqg_join_asof: routes, distinct build tuples and the ordering step's digit passes of the last call (aqg_join_asof_last)
     uint32_t wj_routes = 0, wj_groups = 0, wj_passes = 0;         // aqg_join_window* / aqg_interval_fold: the same of the last call, plus the fold's route (aqg_join_window_last)
+    uint32_t rank_routes = 0, rank_tile = 0;    // aqg_rank*: routes of the last call and the sorted entries one workgroup of its emit kernel owns (aqg_rank_last)
     uint32_t winq_tile = 0, winq_halo = 0;      // aqg_window_quantiles*: rows per workgroup and halo rows of the last call (aqg_window_quantiles_last)
     // aqg_rangew*: the packed step counters of the last bounds call (rising steps in the low word, falling in the high one) and the
     // row count of the last fold, from which aqg_rangew_last derives the block tree's geometry
@@ -149,6 +150,22 @@ static inline void* aqg_pool_alloc(aqg_ctx* ctx, size_t need, size_t* cap, hipEr
     *cap = need;
     return q;
 }
+// a device buffer from the context's pool, given back when the call ends (for what must outlive a workspace reset between the steps of a call)
+struct PoolBuf {
+    aqg_ctx* ctx;
+    void* p = nullptr;
+    size_t cap = 0;
+    explicit PoolBuf(aqg_ctx* c) : ctx(c) {}
+    PoolBuf(const PoolBuf&) = delete;
+    PoolBuf& operator=(const PoolBuf&) = delete;
+    ~PoolBuf() { aqg_pool_give(ctx, p, cap); }
+    int get(size_t bytes) {
+        hipError_t e = hipSuccess;
+        p = aqg_pool_alloc(ctx, bytes < 256 ? 256 : bytes, &cap, &e);
+        if (!p) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return AQG_ERR_NOMEM; }
+        return AQG_OK;
+    }
+};
 // grow-only device buffer of a handle: *p holds at least `need` bytes afterwards (its contents are not kept)
 template <class T> static inline int aqg_dev_realloc(aqg_ctx* ctx, T** p, size_t* cap, size_t need) {
     if (need <= *cap && *p) return AQG_OK;

@@ -92,23 +92,6 @@ __global__ void __launch_bounds__(256) asof_image_kernel(int kind, const void* _
         img[j] = on_img<U>(kind, on_raw(kind, on, srt ? srt[j] : j));
 }
 
-// a device buffer from the context's pool, given back when the call ends (the workspace is reset by the steps in between)
-struct PoolBuf {
-    aqg_ctx* ctx;
-    void* p = nullptr;
-    size_t cap = 0;
-    explicit PoolBuf(aqg_ctx* c) : ctx(c) {}
-    PoolBuf(const PoolBuf&) = delete;
-    PoolBuf& operator=(const PoolBuf&) = delete;
-    ~PoolBuf() { aqg_pool_give(ctx, p, cap); }
-    int get(size_t bytes) {
-        hipError_t e = hipSuccess;
-        p = aqg_pool_alloc(ctx, bytes < 256 ? 256 : bytes, &cap, &e);
-        if (!p) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return AQG_ERR_NOMEM; }
-        return AQG_OK;
-    }
-};
-
 // ---- the entry checks of both joins -----------------------------------------------------------------------------------------------------
 struct JoinSides {
     int nkeys; const int* dts; const void* const* bk; const void* build_on; uint32_t nb;

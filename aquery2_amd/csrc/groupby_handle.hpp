@@ -59,6 +59,8 @@ struct aqg_groupby {
     size_t cap_flat_off = 0, cap_flat_heads = 0, cap_flat_short = 0, cap_flat_gid = 0;
     bool flat_valid = false, flat_gid_valid = false;
     uint32_t flat_short_w = 0;        // flat_short marks the heads of groups with at most this many rows (ratiow's degenerate window); 0: not made
+    // rank.hip: the rows in groups of more than rank_big_max rows (those the SORTED route ranks), read from the device once per layout
+    bool rank_big_valid = false; uint32_t rank_big_max = 0, rank_big_rows = 0;
     // aqg_groupby_merge_packed: the concatenated shard tables (keys / values), owned by the merged handle
     void* xkeys = nullptr; void* xvals = nullptr;
     size_t cap_xkeys = 0, cap_xvals = 0;

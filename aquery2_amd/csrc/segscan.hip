@@ -155,6 +155,7 @@ int ensure_flat(aqg_ctx* ctx, aqg_groupby* g) {
     g->flat_valid = true;
     g->flat_gid_valid = false;
     g->flat_short_w = 0;
+    g->rank_big_valid = false;
     return AQG_OK;
 }
 int ensure_short(aqg_ctx* ctx, aqg_groupby* g, uint32_t w) {

@@ -195,6 +195,13 @@ template <class U> __device__ inline bool digit_step(SelState& st, uint32_t c, u
 }
 
 // ---- routing: one lane per group ------------------------------------------------------------------------------------------------------------
+// SMALL group g (rows from lo) -> tile_first of the tile it starts in, when it can be the first SMALL group that starts there: only a
+// group whose predecessor starts in another tile, or is not SMALL, can be it
+__device__ inline void small_tile_mark(const uint32_t* __restrict__ off, uint32_t g, uint32_t lo, uint32_t small_max, uint32_t* __restrict__ tile_first) {
+    bool first = g == 0;
+    if (!first) { const uint32_t plo = off[g - 1], pc = lo - plo; first = plo / TILE != lo / TILE || pc > small_max || pc == 0; }
+    if (first) atomicMin(&tile_first[lo / TILE], g);
+}
 // The body of a family's classify kernel: SMALL groups mark the first of them that starts in each tile (tile_first), GROUP groups go to
 // glist, and a SPLIT group takes the next number s of the split list and init_split(g, lo, hi, c, s) writes its state(s).
 template <class F>
@@ -206,10 +213,7 @@ __device__ inline void classify_groups(const uint32_t* __restrict__ off, uint32_
         if (c == 0) continue;
         if (c <= small_max) {
             mask |= ROUTE_SMALL;
-            // the first SMALL group that starts in its tile: only a group whose predecessor starts in another tile, or is not SMALL, can be it
-            bool first = g == 0;
-            if (!first) { const uint32_t plo = off[g - 1], pc = lo - plo; first = plo / TILE != lo / TILE || pc > small_max || pc == 0; }
-            if (first) atomicMin(&tile_first[lo / TILE], g);
+            small_tile_mark(off, g, lo, small_max, tile_first);
         } else if (c < split_min) {
             mask |= ROUTE_GROUP;
             glist[atomicAdd(&ctl[CTL_NGROUP], 1u)] = g;
@@ -230,9 +234,11 @@ __device__ inline void classify_groups(const uint32_t* __restrict__ off, uint32_
 //   pair(g, lo, c, a_first)        group g has c = 1 or 2 rows (a lane each, from the column itself); a_first: x[lo] is its first row in order
 //   ranks(c) -> r                  once per group of 3 .. small_max rows: what its rows' ranks are compared with
 //   ranked(g, lo, r, ii, less)     row lo + ii of such a group has rank `less` (rows that sort before it, ties by position)
-template <class U, int KIND, class P, class K, class R>
+//   whole(g, lo, c, im)            (optional; rank.hip) takes the place of ranks / ranked: a wavefront gets the c staged images im[0 .. c) of such
+//                                  a group and does its own counting (ties, distinct values)
+template <class U, int KIND, class P, class K, class R, class W = std::nullptr_t>
 __device__ inline void small_tile(const U* __restrict__ x, uint32_t n, const uint32_t* __restrict__ off, uint32_t G, const uint32_t* __restrict__ tile_first, uint32_t small_max,
-                                  P&& pair, K&& ranks, R&& ranked) {
+                                  P&& pair, K&& ranks, R&& ranked, W&& whole = nullptr) {
     constexpr uint32_t V = 16 / sizeof(U), ROWS = TILE + SMALL_CAP, PER = (ROWS / V + SB - 1) / SB;
     __shared__ U img[ROWS];
     __shared__ uint32_t goff[TILE + 2];
@@ -288,6 +294,7 @@ __device__ inline void small_tile(const U* __restrict__ x, uint32_t n, const uin
         const uint32_t lo = goff[gi], c = goff[gi + 1] - lo;
         if (c < 3 || c > small_max) continue;
         const uint32_t base = lo - tbeg;
+        if constexpr (!std::is_same_v<std::decay_t<W>, std::nullptr_t>) { whole(g0 + gi, lo, c, &img[base]); continue; }
         const auto r = ranks(c);
         for (uint32_t eb = 0; eb < c; eb += 64) {
             const bool live = eb + lane < c;

@@ -334,6 +334,48 @@ int aqg_grouped_window_quantiles(aqg_ctx* ctx, struct aqg_groupby* g, int which,
 int aqg_grouped_window_quantiles_flat(aqg_ctx* ctx, struct aqg_groupby* g, int which, uint32_t nq, const uint32_t* num_host, uint32_t den, int t, const void* xflat, uint32_t w, void* out_flat_dev);
 int aqg_window_quantiles_last(aqg_ctx* ctx, uint32_t* tile_rows, uint32_t* halo_rows);
 
+/* ---- ranking -------------------------------------------------------------------
+ * Where every row stands in its slice: SQL's RANK / DENSE_RANK / ROW_NUMBER / PERCENT_RANK / CUME_DIST / NTILE(k) OVER (PARTITION BY
+ * ... ORDER BY x), pandas' groupby().rank(method=...), kdb's rank / xrank -- for all groups in one call, rows never moved (DESIGN.md
+ * section 4.19).  THE REFERENCE HAS NO SUCH FUNCTION; the contract is this comment, held by the exact model tests/rank_model.py.
+ * Slice: the whole column, or a group's range [offsets[g], offsets[g+1]) of the flat layout; c is its row count.  Ranks are 1-based.
+ * out[i] answers row i of the layout scanned; the grouped forms write the FLAT LAYOUT, like aqg_grouped_scan.
+ * Order: that of aqg_sort_rows under AQG_ORDER_ASC or AQG_ORDER_DESC (AQG_ORDER_NEG: AQG_ERR_ARG, as for top-k).  Integers and BOOL by
+ * value.  Floating columns: -0.0 and +0.0 tie; every NaN is one value and all NaNs tie; NaN sorts after +inf under ASC and before it
+ * under DESC -- pandas' na_option='bottom' (ASC) resp. 'top' (DESC).  Under DESC, FIRST still breaks ties by ascending position.
+ * NTILE(k): with q = c / k, r = c % k and o the 0-based FIRST rank, the bucket is o / (q + 1) + 1 when o < r (q + 1), else
+ * r + (o - r (q + 1)) / q + 1 (SQL's distribution: the first r buckets hold one row more).  k >= 1, else AQG_ERR_ARG; k > c gives
+ * bucket o + 1.  Every other method ignores k.
+ * Exactness: the integer methods are exact.  AVERAGE is exact in double (min + max < 2^33).  PERCENT and CUME_DIST are ONE IEEE double
+ * division of two exactly converted integers.  Results are bit-reproducible from call to call.
+ * Dtypes: those of aqg_median; anything else, the 128-bit integers included, returns AQG_ERR_DTYPE.  AQG_ERR_ARG: a handle of
+ * aqg_groupby_agg, `out` overlapping `x`, an unknown method or order, a NULL column with rows.  Every error returns with nothing
+ * written; n == 0 or G == 0: AQG_OK.
+ *   aqg_rank               the whole column
+ *   aqg_grouped_rank       every group's rows, x in ROW layout (brought into the flat layout in workspace)
+ *   aqg_grouped_rank_flat  the same over a column already in the FLAT LAYOUT of the build
+ * The input is never modified.  Asynchronous on the context's stream, no allocation in steady state, one writer per output element, no
+ * atomics on the result, and a number of launches that does not depend on G.  Groups of up to AQG_SELECT_SMALL_MAX rows are ranked by
+ * comparison in LDS (SMALL); every other group through the stable sort of (group, x) and one rank-emit pass over the order (SORTED,
+ * which reads the sort's digit histogram back as aqg_sort_rows does); one call takes both routes when its groups ask for both.  The
+ * number of rows in groups above the SMALL threshold is read from the device ONCE PER HANDLE and cached in it.
+ * aqg_rank_last: the mask of routes the last call on this context took (AQG_RANK_ROUTE_*) and the entries of the sorted order one
+ * workgroup of the emit kernel owns -- a diagnostic: the tests put tie runs and group starts on the kernel's real tile edges with it. */
+enum { AQG_RANK_MIN = 0,       /* SQL RANK, pandas 'min': 1 + rows of the slice that sort strictly before       -> uint32 */
+       AQG_RANK_MAX = 1,       /* pandas 'max': rows that sort before or tie                                    -> uint32 */
+       AQG_RANK_DENSE = 2,     /* DENSE_RANK: 1 + distinct values that sort strictly before                     -> uint32 */
+       AQG_RANK_FIRST = 3,     /* ROW_NUMBER, pandas 'first': ties by ascending position in the layout scanned  -> uint32 */
+       AQG_RANK_AVERAGE = 4,   /* pandas default: (min + max) / 2, exact                                        -> double */
+       AQG_RANK_PERCENT = 5,   /* PERCENT_RANK: (min - 1) / (c - 1), 0 when c == 1                              -> double */
+       AQG_RANK_CUME_DIST = 6, /* CUME_DIST: max / c                                                            -> double */
+       AQG_RANK_NTILE = 7 };   /* NTILE(k): bucket 1..k of the FIRST rank, SQL's distribution (above)           -> uint32 */
+enum { AQG_RANK_ROUTE_SMALL = 1, AQG_RANK_ROUTE_SORTED = 2 };
+int aqg_rank_out_dtype(int method);   /* AQG_UINT32 or AQG_DOUBLE; -1 for an unknown method */
+int aqg_rank(aqg_ctx* ctx, int method, int order, uint32_t k, int t, const void* x, uint32_t n, void* out_dev);
+int aqg_grouped_rank(aqg_ctx* ctx, struct aqg_groupby* g, int method, int order, uint32_t k, int t, const void* x, void* out_flat_dev);
+int aqg_grouped_rank_flat(aqg_ctx* ctx, struct aqg_groupby* g, int method, int order, uint32_t k, int t, const void* xflat, void* out_flat_dev);
+int aqg_rank_last(aqg_ctx* ctx, uint32_t* routes_host, uint32_t* tile_rows_host);
+
 /* ---- exponential moving averages ------------------------------------------------
  * The decayed averages beside avgs / avgw: kdb's `ema`, pandas' `ewm(...).mean()`, "decayed price by symbol".  THE REFERENCE HAS NO SUCH
  * FUNCTION (server/aggregations.h stops at the windows): these entries stand in for the host loop per group a user would otherwise

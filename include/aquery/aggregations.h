@@ -133,6 +133,30 @@ template <class T, template <typename...> class VT, class Ret> inline void devic
     } else dev::check(aqg_scan_ema(rt.ctx(), mode, dev::tag_of<std::remove_cv_t<T>>::value, in.d, n, alpha, nullptr, static_cast<double*>(dout)), "aqg_scan_ema");
     if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
 }
+// ret = the rank of every element of arr in arr (include/aqg.h, ranking section): method AQG_RANK_*, order AQG_ORDER_ASC / DESC, k the
+// buckets of NTILE; `ret` holds uint32_t, or doubles for AVERAGE / PERCENT / CUME_DIST.  A per-group temporary of the generated loop that
+// is ALL of its group is answered for all groups by one aqg_grouped_rank_flat (Runtime::vcol_rank) and `ret` becomes this group's slice
+// of that result; any other vector goes through aqg_rank on its own rows.
+template <class T, template <typename...> class VT, class Ret> inline void device_rank(int method, int order, uint32_t k, const VT<T>& arr, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    static_assert(std::is_same_v<RT, uint32_t> || std::is_same_v<RT, double>, "rank: the result holds uint32_t or doubles");
+    if ((aqg_rank_out_dtype(method) == AQG_DOUBLE) != std::is_same_v<RT, double>) dev::check(AQG_ERR_ARG, "rank: the result's element type does not fit the method");
+    auto& rt = dev::Runtime::get();
+    const uint32_t n = arr.size;
+    if (n == 0) return;
+    if (rt.deferred_whole(arr.container, n)) {
+        dev::Entry* e = rt.deferred_at(arr.container);
+        dev::GroupCtx* gc = e->dgroup;
+        const uint32_t g = e->dg;
+        rt.defer_slice(ret.container, (size_t)n * sizeof(RT), gc, g, rt.vcol_rank(gc, e->dv, method, order, k));
+        if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+        return;
+    }
+    void* dout = rt.result(ret.container, (size_t)n * sizeof(RT));
+    dev::In in(arr.container, (size_t)n * sizeof(T), arr.capacity == 0);
+    dev::check(aqg_rank(rt.ctx(), method, order, k, dev::tag_of<std::remove_cv_t<T>>::value, in.d, n, dout), "aqg_rank");
+    if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+}
 // ret = decay(halflife, t): 2^(-|t[i] - t[i-1]| / halflife), 1 at the first element; a per-group temporary that is all of its group: one
 // aqg_grouped_decay_from_times_flat for all groups (Runtime::vcol_decay)
 template <class T, template <typename...> class VT, class Ret> inline void device_decay(double halflife, const VT<T>& t, Ret& ret) {
@@ -424,6 +448,28 @@ AQ_EMAD(emad, AQG_EMA_RECURSIVE)
 AQ_EMAD(ewmad, AQG_EMA_ADJUSTED)
 #undef AQ_EMA
 #undef AQ_EMAD
+// rank(v) / dense_rank(v) / row_number(v) / avg_rank(v) / percent_rank(v) / cume_dist(v) / ntile(k, v): where every element stands in v, 1-based
+// -- SQL's RANK, DENSE_RANK, ROW_NUMBER, PERCENT_RANK, CUME_DIST and NTILE(k) OVER (ORDER BY v), pandas' rank(method='min' / 'dense' /
+// 'first' / 'average'), with ties and NaNs as order_by sorts them; a trailing `true` ranks in descending order.  uint32_t, or doubles for
+// avg_rank / percent_rank / cume_dist; the reference's header has none of them (include/aqg.h, ranking section).  rankof is the name
+// generated code can use for rank: under its `using namespace std` a call to `rank` is ambiguous with std::rank.
+#define AQ_RANK(name, method, R)                                                                                   \
+    template <class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T> && !std::is_arithmetic_v<Ret>>* = nullptr> \
+    void name(const VT<T>& arr, Ret& ret, bool desc = false) { aq::device_rank(method, desc ? AQG_ORDER_DESC : AQG_ORDER_ASC, 0, arr, ret); } \
+    template <class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T>>* = nullptr>             \
+    inline decayed_t<VT, R> name(const VT<T>& arr, bool desc = false) { decayed_t<VT, R> ret(arr.size); name(arr, ret, desc); return ret; }
+AQ_RANK(rank, AQG_RANK_MIN, uint32_t)
+AQ_RANK(rankof, AQG_RANK_MIN, uint32_t)
+AQ_RANK(dense_rank, AQG_RANK_DENSE, uint32_t)
+AQ_RANK(row_number, AQG_RANK_FIRST, uint32_t)
+AQ_RANK(avg_rank, AQG_RANK_AVERAGE, double)
+AQ_RANK(percent_rank, AQG_RANK_PERCENT, double)
+AQ_RANK(cume_dist, AQG_RANK_CUME_DIST, double)
+#undef AQ_RANK
+template <class K, class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T> && std::is_integral_v<K> && !std::is_arithmetic_v<Ret>>* = nullptr>
+void ntile(K k, const VT<T>& arr, Ret& ret, bool desc = false) { aq::device_rank(AQG_RANK_NTILE, desc ? AQG_ORDER_DESC : AQG_ORDER_ASC, (uint32_t)k, arr, ret); }
+template <class K, class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T> && std::is_integral_v<K>>* = nullptr>
+inline decayed_t<VT, uint32_t> ntile(K k, const VT<T>& arr, bool desc = false) { decayed_t<VT, uint32_t> ret(arr.size); ntile(k, arr, ret, desc); return ret; }
 // (decayt is the name generated code can use: under its `using namespace std` a call to `decay` is ambiguous with std::decay)
 #define AQ_DECAY(name)                                                                                            \
     template <class H, class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T> && std::is_arithmetic_v<H>>* = nullptr> \

@@ -278,6 +278,22 @@ public:
         if (rc != AQG_OK) die("aqg_grouped_ema_flat", rc, ctx_);
         return vcol_new(c, key, r);
     }
+    // the rank (method: AQG_RANK_*, order: AQG_ORDER_ASC / DESC, k: NTILE's buckets) of every row of every group's slice: ONE
+    // aqg_grouped_rank_flat over the flat column per (column, method, order, k), whatever the number of groups
+    size_t grouped_rank_calls = 0;              // aqg_grouped_rank_flat calls made so far (the tests count them)
+    int vcol_rank(GroupCtx* c, int v, int method, int order, uint32_t k) {
+        const std::array<uint64_t, 6> key{9, (uint64_t)method, (uint64_t)v, (uint64_t)order, method == AQG_RANK_NTILE ? k : 0u, 0};
+        auto it = c->memo.find(key);
+        if (it != c->memo.end()) return it->second;
+        VCol r; r.layout = 1; r.tag = aqg_rank_out_dtype(method);
+        const void* xf = vcol_flat_ptr(c, v);
+        int rc = aqg_malloc(ctx(), (size_t)c->n * esz(r.tag) + 16, &r.dptr);
+        if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+        ++grouped_rank_calls;
+        rc = aqg_grouped_rank_flat(ctx_, c->handle, method, order, k, c->vcols[v].tag, xf, r.dptr);
+        if (rc != AQG_OK) die("aqg_grouped_rank_flat", rc, ctx_);
+        return vcol_new(c, key, r);
+    }
     // decay(halflife, t) of every group's slice: one aqg_grouped_decay_from_times_flat over the flat column
     int vcol_decay(GroupCtx* c, int v, double halflife) {
         uint64_t hbits;
