@@ -133,6 +133,24 @@ STR_ROUTE_HOST, STR_ROUTE_DEVICE, STR_ROUTE_FALLBACK = 1, 2, 4                  
 STR_PROTOTYPES = {
     "aqg_str_encode_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
 }
+# the scratch-memory guard (test aids of include/aqg.h; on in a process started with AQG_WS_GUARD=<byte>)
+WS_CLEAN, WS_ZONE, WS_PADDING, WS_TAIL, WS_RANK_BM = range(5)
+
+
+class WsReport(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("alloc_index", C.c_int32), ("offset", C.c_uint64), ("alloc_offset", C.c_uint64),
+                ("alloc_bytes", C.c_uint64), ("expected", C.c_uint8), ("found", C.c_uint8), ("pad_", C.c_uint8 * 6)]
+
+
+class WsInfo(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("physical_bytes", C.c_uint64), ("logical_bytes", C.c_uint64), ("rank_bm", C.c_void_p),
+                ("rank_bm_bytes", C.c_uint64), ("nallocs", C.c_uint32), ("guard", C.c_uint8), ("pattern", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+DEBUG_PROTOTYPES = {
+    "aqg_debug_ws_check": [C.c_void_p, C.POINTER(WsReport)],
+    "aqg_debug_ws_info": [C.c_void_p, C.POINTER(WsInfo), C.c_void_p, C.c_uint32],
+}
 PLAN_FAST_LDS, PLAN_SMALL_LDS, PLAN_BIG_LDS, PLAN_DENSE, PLAN_PART_ONE, PLAN_PART_TWO, PLAN_PART_ROUND1, PLAN_PART_WIDE, PLAN_SORTED_TAIL, PLAN_HBM_TABLE, PLAN_BUILD_PARTITIONED, PLAN_GID_PARTITION, PLAN_PACKED_VALUES, PLAN_RANGE_PARTITIONS, PLAN_ROW_EMIT, PLAN_PACKED_KEYS, PLAN_BUILD_LOOKUP = (1 << i for i in range(17))
 
 
@@ -167,7 +185,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(RANK_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()) + list(WJ_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(RANK_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()) + list(WJ_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -1188,6 +1206,26 @@ class Device:
         return out.to_host()
 
     # -- timing
+    def debug_ws_check(self):
+        """aqg_debug_ws_check: run the scratch-memory check; the latched report as a dict (kind WS_CLEAN: nothing damaged)"""
+        r = WsReport()
+        self._chk(self.lib.aqg_debug_ws_check(self.ctx, C.byref(r)), "aqg_debug_ws_check")
+        return {"kind": r.kind, "alloc_index": r.alloc_index, "offset": r.offset, "alloc_offset": r.alloc_offset,
+                "alloc_bytes": r.alloc_bytes, "expected": r.expected, "found": r.found}
+
+    def debug_ws_info(self):
+        """aqg_debug_ws_info: the arena of the last use and its logged sub-allocations [(physical offset, bytes), ...]"""
+        i = WsInfo()
+        self._chk(self.lib.aqg_debug_ws_info(self.ctx, C.byref(i), None, 0), "aqg_debug_ws_info")
+        a = np.zeros(2 * max(1, i.nallocs), np.uint64)
+        self._chk(self.lib.aqg_debug_ws_info(self.ctx, C.byref(i), a.ctypes.data_as(C.c_void_p), i.nallocs), "aqg_debug_ws_info")
+        return {"base": i.base or 0, "physical_bytes": i.physical_bytes, "logical_bytes": i.logical_bytes, "rank_bm": i.rank_bm or 0,
+                "rank_bm_bytes": i.rank_bm_bytes, "guard": bool(i.guard), "pattern": i.pattern,
+                "allocs": [(int(a[2 * k]), int(a[2 * k + 1])) for k in range(i.nallocs)]}
+
+    def memset(self, ptr, byte, nbytes):
+        self._chk(self.lib.aqg_memset(self.ctx, C.c_void_p(ptr), int(byte), C.c_size_t(nbytes)), "aqg_memset")
+
     def timer_start(self):
         self._chk(self.lib.aqg_timer_start(self.ctx), "aqg_timer_start")
 

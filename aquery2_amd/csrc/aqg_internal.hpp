@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/aqg.h"
+#include "ws_guard.hpp"
 
 // device mirror of a borrowed host column: `regs` = the host ranges page-locked for its upload (released at unpin), `ev` = upload done
 struct aqg_pin { void* dptr; size_t bytes; std::vector<std::pair<void*, size_t>> regs; hipEvent_t ev; };
@@ -24,6 +25,7 @@ struct aqg_ctx {
     // workspace arena: one allocation, bump-allocated per API call
     char* ws = nullptr;
     size_t ws_cap = 0, ws_off = 0;
+    ws_guard_book guard;                         // AQG_WS_GUARD (test aid): ws_off is then the LOGICAL bump offset, ws_cap the physical size (ws_guard.hpp)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t evk0 = nullptr, evk1 = nullptr;   // bracket the dominant kernel of the last call
     hipEvent_t ev_flags = nullptr;               // recorded behind the copy of a group table's flag words (run_agg)
@@ -108,8 +110,20 @@ struct aqg_switch_set {
     uint32_t select_small_max, select_split_min;   // AQG_SELECT_SMALL_MAX (256), AQG_SELECT_SPLIT_MIN (2^20): the route thresholds of select.hip
     double pw_sigma;                    // AQG_PW_SIGMA (6)
     bool disable_p1, disable_p1_cursors, disable_ranged, disable_pw_defer, disable_build_partition, debug_flags, str_host;
+    int ws_guard;                       // AQG_WS_GUARD=<byte>: poison, red zones and exact sizing of the scratch memory (-1: unset)
 };
 const aqg_switch_set& aqg_switches();
+// AQG_WS_GUARD: fill fresh or recycled device scratch of the library with the poison byte (nothing when the switch is unset)
+static inline void aqg_guard_fill(aqg_ctx* ctx, void* p, size_t bytes) {
+    if (ctx->guard.on && p && bytes) (void)hipMemsetAsync(p, ctx->guard.pattern, bytes, ctx->stream);
+}
+// hipMalloc of device scratch the library keeps for itself (control words, grow-only lists): poisoned under AQG_WS_GUARD
+static inline hipError_t aqg_scratch_malloc(aqg_ctx* ctx, void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) aqg_guard_fill(ctx, *p, bytes);
+    return e;
+}
+template <class T> static inline hipError_t aqg_scratch_malloc(aqg_ctx* ctx, T** p, size_t bytes) { return aqg_scratch_malloc(ctx, reinterpret_cast<void**>(p), bytes); }
 
 // workspace: reset at the start of an API call, then bump.  Growing synchronises the
 // stream (earlier kernels may still read the old arena) -- call aqg_reserve_workspace
@@ -142,12 +156,13 @@ static inline void aqg_pool_give(aqg_ctx* ctx, void* p, size_t cap) {
 }
 // `need` bytes from the pool, else from hipMalloc (*err: its status); nullptr, and no error left behind for the next launch check, when there is no memory
 static inline void* aqg_pool_alloc(aqg_ctx* ctx, size_t need, size_t* cap, hipError_t* err = nullptr) {
-    if (void* q = aqg_pool_take(ctx, need, cap)) return q;
+    if (void* q = aqg_pool_take(ctx, need, cap)) { aqg_guard_fill(ctx, q, *cap); return q; }
     void* q = nullptr;
     const hipError_t e = hipMalloc(&q, need);
     if (err) *err = e;
     if (e != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     *cap = need;
+    aqg_guard_fill(ctx, q, need);
     return q;
 }
 // a device buffer from the context's pool, given back when the call ends (for what must outlive a workspace reset between the steps of a call)

@@ -74,6 +74,7 @@ int aqg_ctx_create(int device, void* hip_stream, aqg_ctx** out) {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return AQG_ERR_NODEVICE;
     aqg_ctx* ctx = new aqg_ctx();
     ctx->device = device;
+    if (aqg_switches().ws_guard >= 0) { ctx->guard.on = true; ctx->guard.pattern = (uint8_t)aqg_switches().ws_guard; }
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return AQG_ERR_NODEVICE; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -136,6 +137,7 @@ int aqg_sync(aqg_ctx* ctx) {
 
 int aqg_reserve_workspace(aqg_ctx* ctx, size_t bytes) {
     if (!ctx) return AQG_ERR_ARG;
+    if (ctx->guard.on) AQG_TRY(aqg_ws_reset(ctx));       // (the arena holds nothing across calls; under the guard a request belongs to one use)
     return aqg_ws_ensure(ctx, bytes);
 }
 
@@ -423,16 +425,89 @@ const aqg_switch_set& aqg_switches() {
         .pw_sigma = getenv("AQG_PW_SIGMA") ? atof(getenv("AQG_PW_SIGMA")) : 6.0,
         .disable_p1 = set("AQG_DISABLE_P1"), .disable_p1_cursors = set("AQG_DISABLE_P1_CURSORS"), .disable_ranged = set("AQG_DISABLE_RANGED"),
         .disable_pw_defer = set("AQG_DISABLE_PW_DEFER"), .disable_build_partition = set("AQG_DISABLE_BUILD_PARTITION"),
-        .debug_flags = set("AQG_DEBUG_FLAGS"), .str_host = set("AQG_STR_HOST")};
+        .debug_flags = set("AQG_DEBUG_FLAGS"), .str_host = set("AQG_STR_HOST"),
+        .ws_guard = getenv("AQG_WS_GUARD") ? (int)(strtoul(getenv("AQG_WS_GUARD"), nullptr, 0) & 0xFF) : -1};
     return s;
 }
 
 // ---- workspace arena ---------------------------------------------------------------------------
+// AQG_WS_GUARD: every byte of the arena outside the payloads logged since the last reset still holds the poison byte, and the ranking
+// bitmap is all zero; the first violation is latched in the context (ws_guard.hpp).  Synchronises the stream.
+static int guard_check(aqg_ctx* ctx) {
+    ws_guard_book& g = ctx->guard;
+    if (!g.on) return AQG_OK;
+    AQG_HIP(ctx, hipSetDevice(ctx->device));
+    AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint8_t> host;
+    if (ctx->ws && ctx->ws_cap) {
+        host.resize(ctx->ws_cap);
+        AQG_HIP(ctx, hipMemcpy(host.data(), ctx->ws, ctx->ws_cap, hipMemcpyDeviceToHost));
+        g.latch(ws_guard_scan(host.data(), ctx->ws_cap, g.pattern, g.log));
+    }
+    if (ctx->rank_bm && ctx->rank_bm_words) {
+        host.resize(ctx->rank_bm_words * 4);
+        AQG_HIP(ctx, hipMemcpy(host.data(), ctx->rank_bm, host.size(), hipMemcpyDeviceToHost));
+        const size_t m = ws_guard_detail::first_mismatch(host.data(), 0, host.size(), 0);
+        if (m < host.size()) {
+            ws_guard_report r;
+            r.kind = WS_GUARD_RANK_BM; r.offset = m; r.expected = 0; r.found = host[m];
+            g.latch(r);
+        }
+    }
+    return AQG_OK;
+}
+extern "C" int aqg_debug_ws_check(aqg_ctx* ctx, aqg_ws_report* out) {
+    if (!ctx || !out) return AQG_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    if (!ctx->guard.on) return aqg_fail(ctx, AQG_ERR_ARG, "aqg_debug_ws_check: AQG_WS_GUARD is not set");
+    AQG_TRY(guard_check(ctx));
+    const ws_guard_report& r = ctx->guard.latched;
+    out->kind = (uint32_t)r.kind; out->alloc_index = r.after; out->offset = r.offset;
+    out->alloc_offset = r.after_off; out->alloc_bytes = r.after_bytes; out->expected = r.expected; out->found = r.found;
+    return AQG_OK;
+}
+extern "C" int aqg_debug_ws_info(aqg_ctx* ctx, aqg_ws_info* out, uint64_t* allocs, uint32_t max_allocs) {
+    if (!ctx || !out) return AQG_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    const ws_guard_book& g = ctx->guard;
+    out->guard = g.on ? 1 : 0; out->pattern = g.pattern;
+    out->base = ctx->ws; out->physical_bytes = ctx->ws_cap; out->logical_bytes = g.on ? g.logical_cap : ctx->ws_cap;      // (logical: of the current use)
+    out->nallocs = (uint32_t)g.log.size();
+    out->rank_bm = ctx->rank_bm; out->rank_bm_bytes = (uint64_t)ctx->rank_bm_words * 4;
+    for (uint32_t i = 0; allocs && i < max_allocs && i < g.log.size(); ++i) { allocs[2 * i] = g.log[i].off; allocs[2 * i + 1] = g.log[i].bytes; }
+    return AQG_OK;
+}
+
 int aqg_ws_reset(aqg_ctx* ctx) {
     ctx->ws_off = 0;
+    if (ctx->guard.on) {
+        AQG_TRY(guard_check(ctx));           // what the arena's last use left behind, before the poison covers it
+        ctx->guard.reset();
+        if (ctx->ws) AQG_HIP(ctx, hipMemsetAsync(ctx->ws, ctx->guard.pattern, ctx->ws_cap, ctx->stream));
+    }
+    return AQG_OK;
+}
+// the guarded arena: the use's logical capacity is exactly what was asked for since the reset; the physical arena (capacity + zones) only
+// grows, is replaced -- and poisoned -- when a use needs more, and never under live sub-allocations
+static int guard_ensure(aqg_ctx* ctx, size_t bytes) {
+    ws_guard_book& g = ctx->guard;
+    if (!g.want(bytes)) return aqg_fail(ctx, AQG_ERR_NOMEM, "workspace grown under live sub-allocations (internal sizing bug)");
+    const size_t cap = g.physical_cap();
+    if (ctx->ws && cap <= ctx->ws_cap) return AQG_OK;
+    if (g.live()) return aqg_fail(ctx, AQG_ERR_NOMEM, "workspace grown under live sub-allocations (internal sizing bug)");
+    AQG_HIP(ctx, hipSetDevice(ctx->device));
+    AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->ws) { hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_cap = 0; }
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, cap);
+    if (e != hipSuccess) { ctx->err = std::string("workspace hipMalloc: ") + hipGetErrorString(e); (void)hipGetLastError(); return AQG_ERR_NOMEM; }
+    ctx->ws = static_cast<char*>(p);
+    ctx->ws_cap = cap;
+    AQG_HIP(ctx, hipMemsetAsync(ctx->ws, g.pattern, cap, ctx->stream));
     return AQG_OK;
 }
 int aqg_ws_ensure(aqg_ctx* ctx, size_t bytes) {
+    if (ctx->guard.on) return guard_ensure(ctx, bytes);
     if (bytes <= ctx->ws_cap) return AQG_OK;
     AQG_HIP(ctx, hipSetDevice(ctx->device));
     AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -452,6 +527,20 @@ int aqg_ws_ensure(aqg_ctx* ctx, size_t bytes) {
 // NOTE: a grow in the middle of a call would invalidate earlier sub-allocations of the same
 // call, so every API entry computes its total need first and calls aqg_ws_ensure once.
 int aqg_ws_alloc(aqg_ctx* ctx, size_t bytes, void** out) {
+    if (ctx->guard.on) {
+        ws_guard_book& g = ctx->guard;
+        size_t phys = 0;
+        int rc = g.alloc(&ctx->ws_off, bytes, &phys);
+        if (rc == 1 && ctx->ws_off == 0) {       // (the first sub-allocation of a use may size the arena, as below)
+            AQG_TRY(aqg_ws_ensure(ctx, bytes));
+            rc = g.alloc(&ctx->ws_off, bytes, &phys);
+        }
+        if (rc == 1) return aqg_fail(ctx, AQG_ERR_NOMEM, "workspace overflow inside a call (internal sizing bug)");
+        if (rc == 2) return aqg_fail(ctx, AQG_ERR_NOMEM, "AQG_WS_GUARD: more sub-allocations in one arena use than the guard has zones for");
+        if (!ctx->ws) AQG_TRY(aqg_ws_ensure(ctx, 0));
+        *out = ctx->ws + phys;
+        return AQG_OK;
+    }
     size_t off = (ctx->ws_off + 255) & ~(size_t)255;
     if (off + bytes > ctx->ws_cap) {
         if (off != 0) return aqg_fail(ctx, AQG_ERR_NOMEM, "workspace overflow inside a call (internal sizing bug)");

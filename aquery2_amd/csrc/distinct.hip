@@ -200,7 +200,7 @@ __global__ void distinct_add_kernel(uint32_t* out, uint32_t v) { *out += v; }
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
 size_t distinct_ws_bytes(uint32_t n) { return ((size_t)aqg_ceil_div(n, TILE) + 1) * 4 + 4096; }
 int ensure_ctl(aqg_ctx* ctx) {
-    if (!ctx->distinct_ctl) AQG_HIP(ctx, hipMalloc(&ctx->distinct_ctl, 256));
+    if (!ctx->distinct_ctl) AQG_HIP(ctx, aqg_scratch_malloc(ctx, &ctx->distinct_ctl, 256));
     AQG_HIP(ctx, hipMemsetAsync(ctx->distinct_ctl, 0, CTL_WORDS * 4, ctx->stream));
     return AQG_OK;
 }
@@ -211,7 +211,7 @@ int ensure_pairs(aqg_ctx* ctx, size_t bytes) {
     AQG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->distinct_pairs) { (void)hipFree(ctx->distinct_pairs); ctx->distinct_pairs = nullptr; ctx->distinct_pairs_cap = 0; }
     void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
+    const hipError_t e = aqg_scratch_malloc(ctx, &p, bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("count distinct: pair list: ") + hipGetErrorString(e); return AQG_ERR_NOMEM; }
     ctx->distinct_pairs = p;
     ctx->distinct_pairs_cap = bytes;

@@ -106,7 +106,7 @@ int grow(aqg_ctx* ctx, void** p, size_t* cap, size_t need) {
     if (need <= *cap && *p) return AQG_OK;
     if (*p) { AQG_HIP(ctx, hipStreamSynchronize(ctx->stream)); AQG_HIP(ctx, hipFree(*p)); *p = nullptr; *cap = 0; }
     const size_t want = need < 4096 ? 4096 : need;
-    if (hipMalloc(p, want) != hipSuccess) { ctx->err = "exchange: hipMalloc failed"; (void)hipGetLastError(); return AQG_ERR_NOMEM; }
+    if (aqg_scratch_malloc(ctx, p, want) != hipSuccess) { ctx->err = "exchange: hipMalloc failed"; (void)hipGetLastError(); return AQG_ERR_NOMEM; }
     *cap = want;
     return AQG_OK;
 }

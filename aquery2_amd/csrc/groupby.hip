@@ -334,7 +334,7 @@ int agg_workspace(aqg_ctx* ctx, const AggPlan& p, AggBufs* out) {
         if (p.sparse_rank) {
             if (ctx->rank_bm_words < p.nwords) {
                 if (ctx->rank_bm) { AQG_HIP(ctx, hipStreamSynchronize(ctx->stream)); AQG_HIP(ctx, hipFree(ctx->rank_bm)); ctx->rank_bm = nullptr; ctx->rank_bm_words = 0; }
-                if (hipMalloc(&ctx->rank_bm, (size_t)p.nwords * 4) != hipSuccess) { (void)hipGetLastError(); return aqg_fail(ctx, AQG_ERR_NOMEM, "group-by: no memory for the ranking bitmap"); }
+                if (aqg_scratch_malloc(ctx, &ctx->rank_bm, (size_t)p.nwords * 4) != hipSuccess) { (void)hipGetLastError(); return aqg_fail(ctx, AQG_ERR_NOMEM, "group-by: no memory for the ranking bitmap"); }
                 ctx->rank_bm_words = p.nwords;
                 AQG_HIP(ctx, hipMemsetAsync(ctx->rank_bm, 0, (size_t)p.nwords * 4, ctx->stream));
             }

@@ -159,7 +159,7 @@ int check_grouped(aqg_ctx* ctx, const aqg_groupby* g) {
 int run_bounds(aqg_ctx* ctx, aqg_groupby* g, int tt, const void* times, uint32_t n, const span_lim& lim, uint32_t* lo_out) {
     const uint32_t *gid = nullptr, *off = nullptr;
     if (g) { AQG_TRY(aqg_flat_gid(ctx, g, &gid)); off = g->flat_off; }
-    if (!ctx->rangew_steps) AQG_HIP(ctx, hipMalloc(&ctx->rangew_steps, 256));
+    if (!ctx->rangew_steps) AQG_HIP(ctx, aqg_scratch_malloc(ctx, &ctx->rangew_steps, 256));
     AQG_HIP(ctx, hipMemsetAsync(ctx->rangew_steps, 0, 8, ctx->stream));
     const unsigned grid = aqg_ceil_div(n, TS);
     auto go = [&](auto tag) -> int {

@@ -23,7 +23,7 @@ inline size_t select_ws_bytes(uint32_t n, uint32_t G, SelSwitches sw) {
     return rup(((size_t)aqg_ceil_div(n, TILE) + 1) * 4) + rup((size_t)group_cap(n, G, sw.small_max) * 4) + rup((size_t)split_cap(n, G, sw.split_min) * (sizeof(SelState) + 2048)) + 4096;
 }
 inline int ensure_ctl(aqg_ctx* ctx) {
-    if (!ctx->select_ctl) AQG_HIP(ctx, hipMalloc(&ctx->select_ctl, 256));
+    if (!ctx->select_ctl) AQG_HIP(ctx, aqg_scratch_malloc(ctx, &ctx->select_ctl, 256));
     AQG_HIP(ctx, hipMemsetAsync(ctx->select_ctl, 0, CTL_WORDS * 4, ctx->stream));
     return AQG_OK;
 }

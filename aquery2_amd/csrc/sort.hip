@@ -391,7 +391,7 @@ int aqg_sort_rows(aqg_ctx* ctx, int nkeys, const int* key_dtypes, const void* co
         }
     }
     if (m <= SMALL) {
-        if (!ctx->sort_passes_dev) AQG_HIP(ctx, hipMalloc(&ctx->sort_passes_dev, 256));
+        if (!ctx->sort_passes_dev) AQG_HIP(ctx, aqg_scratch_malloc(ctx, &ctx->sort_passes_dev, 256));
         aqg_kernel_timer_begin(ctx);
         hipLaunchKernelGGL(sort_small_kernel, dim3(1), dim3(RB), 0, ctx->stream, segs, rows_in, m, rows_out, ctx->sort_passes_dev);
         aqg_kernel_timer_end(ctx);

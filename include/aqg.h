@@ -872,6 +872,38 @@ int aqg_last_kernel_ms(aqg_ctx* ctx, float* ms_host);
 
 const char* aqg_version(void);
 
+/* ---- test aids ---------------------------------------------------------------
+ * The scratch-memory guard (DESIGN.md "Scratch memory"), on in a process started with AQG_WS_GUARD=<byte>: the workspace arena, the
+ * pooled handle buffers and the library's own control words are filled with that byte before every use; every sub-allocation of the
+ * arena is preceded by a 256-byte red zone (physical offset = logical offset + 256 * (index + 1)); the arena's logical capacity is
+ * exactly the largest size a call has asked for, rounded up to 256.  At every reset of the arena, and on demand, the arena is copied
+ * to the host: every byte outside the sub-allocations made since the last reset must still hold the byte, and the ranking bitmap
+ * must be all zero.  The FIRST violation is latched in the context and stays.
+ *   aqg_debug_ws_check  synchronises, runs the check and returns the latched report (kind AQG_WS_CLEAN: none).  AQG_ERR_ARG when the
+ *                       switch is not set.
+ *   aqg_debug_ws_info   the arena of the last use; with `allocs` != NULL the first max_allocs logged sub-allocations as
+ *                       (physical offset, bytes) pairs of uint64.  Works without the switch too (no log then).                    */
+enum { AQG_WS_CLEAN = 0, AQG_WS_ZONE = 1, AQG_WS_PADDING = 2, AQG_WS_TAIL = 3, AQG_WS_RANK_BM = 4 };
+typedef struct aqg_ws_report {
+    uint32_t kind;          /* AQG_WS_*: what the first damaged byte belongs to                                              */
+    int32_t alloc_index;    /* the logged sub-allocation the byte follows, -1: none                                           */
+    uint64_t offset;        /* physical offset of the byte in the arena (AQG_WS_RANK_BM: byte offset into the bitmap)          */
+    uint64_t alloc_offset, alloc_bytes;   /* that sub-allocation                                                              */
+    uint8_t expected, found;
+    uint8_t pad_[6];
+} aqg_ws_report;
+typedef struct aqg_ws_info {
+    void* base;             /* device address of the arena                                                                    */
+    uint64_t physical_bytes, logical_bytes;
+    void* rank_bm;          /* the ranking bitmap of the few-pass group-by (NULL: never allocated)                              */
+    uint64_t rank_bm_bytes;
+    uint32_t nallocs;       /* sub-allocations logged since the last reset                                                     */
+    uint8_t guard, pattern;
+    uint8_t pad_[2];
+} aqg_ws_info;
+int aqg_debug_ws_check(aqg_ctx* ctx, aqg_ws_report* out);
+int aqg_debug_ws_info(aqg_ctx* ctx, aqg_ws_info* out, uint64_t* allocs, uint32_t max_allocs);
+
 #ifdef __cplusplus
 }
 #endif
