@@ -9,3 +9,5 @@ from . import capi  # noqa: F401
 from .capi import Device, DevBuf, AqgError, Comm, ThreadRanks, lib_path, load_library  # noqa: F401
 from .capi import (RANK_MIN, RANK_MAX, RANK_DENSE, RANK_FIRST, RANK_AVERAGE, RANK_PERCENT, RANK_CUME_DIST, RANK_NTILE,  # noqa: F401
                    RANK_ROUTE_SMALL, RANK_ROUTE_SORTED)
+from .capi import (SCAN2_COVS, SCAN2_CORRS, SCAN2_BETAS, SCAN2_COVW, SCAN2_CORRW, SCAN2_BETAW,  # noqa: F401
+                   SCAN2_ROUTE_REG, SCAN2_ROUTE_LDS, SCAN2_ROUTE_PREFIX)

@@ -68,6 +68,15 @@ RANK_PROTOTYPES = {
     "aqg_grouped_rank_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
     "aqg_rank_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
 }
+# ctypes prototypes of the pair windows (applied by load_library); SCAN2_*: aqg_scan2's ops, SCAN2_ROUTE_*: aqg_scan2_last
+SCAN2_COVS, SCAN2_CORRS, SCAN2_BETAS, SCAN2_COVW, SCAN2_CORRW, SCAN2_BETAW = range(6)
+SCAN2_ROUTE_REG, SCAN2_ROUTE_LDS, SCAN2_ROUTE_PREFIX = 1, 2, 4
+SCAN2_PROTOTYPES = {
+    "aqg_scan2": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "aqg_grouped_scan2": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_grouped_scan2_flat": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p],
+    "aqg_scan2_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+}
 # ctypes prototypes of the exponential moving averages (applied by load_library)
 EMA_RECURSIVE, EMA_ADJUSTED = 0, 1
 EMA_PROTOTYPES = {
@@ -185,7 +194,7 @@ def load_library():
         lib.aqg_groupby_first_rows64.restype = C.c_void_p
         for f in ("aqg_groupby_reversemap", "aqg_groupby_counts", "aqg_groupby_first_rows", "aqg_groupby_agg_result"):
             getattr(lib, f).restype = C.c_void_p
-        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(RANK_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()) + list(WJ_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+        for f, argtypes in list(MEDIAN_PROTOTYPES.items()) + list(TOPK_PROTOTYPES.items()) + list(QUANTILE_PROTOTYPES.items()) + list(WINQ_PROTOTYPES.items()) + list(RANK_PROTOTYPES.items()) + list(SCAN2_PROTOTYPES.items()) + list(EMA_PROTOTYPES.items()) + list(RANGEW_PROTOTYPES.items()) + list(DISTINCT_PROTOTYPES.items()) + list(JOIN_KEYS_PROTOTYPES.items()) + list(STR_PROTOTYPES.items()) + list(ASOF_PROTOTYPES.items()) + list(WJ_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
             getattr(lib, f).argtypes, getattr(lib, f).restype = argtypes, C.c_int
         _LIB = lib
     return _LIB
@@ -828,6 +837,31 @@ class Device:
         """(mask of RANK_ROUTE_* the last rank call took, sorted entries one workgroup of its emit kernel owns)"""
         r, t = C.c_uint32(), C.c_uint32()
         self._chk(self.lib.aqg_rank_last(self.ctx, C.byref(r), C.byref(t)), "aqg_rank_last")
+        return r.value, t.value
+
+    # -- pair windows (moving and running cov / corr / beta of two columns: include/aqg_pair.h)
+    def scan2(self, op, x, y, w=0, keep=False, out=None):
+        """SCAN2_COVW / CORRW / BETAW over the last min(w, i + 1) rows of the two columns, or the running SCAN2_COVS / CORRS / BETAS (w
+        ignored): n doubles, population moments, beta = the slope of y on x"""
+        xd, yd = self._dev(x), self._dev(y)
+        assert xd.n == yd.n
+        out = out if out is not None else self.empty(xd.n, np.float64)
+        self._chk(self.lib.aqg_scan2(self.ctx, op, xd.tag, xd.ptr, yd.tag, yd.ptr, xd.n, w, out.ptr), "aqg_scan2")
+        return out if keep else out.to_host()
+
+    def grouped_scan2(self, gb, op, x, y, w=0, flat=False, keep=False, out=None):
+        """the same within every group of a build, n doubles in the flat layout: `x`, `y` in row layout, or (flat=True) already flat"""
+        xd, yd = self._dev(x), self._dev(y)
+        assert xd.n == yd.n
+        out = out if out is not None else self.empty(xd.n, np.float64)
+        fn = self.lib.aqg_grouped_scan2_flat if flat else self.lib.aqg_grouped_scan2
+        self._chk(fn(self.ctx, gb.h, op, xd.tag, xd.ptr, yd.tag, yd.ptr, w, out.ptr), "aqg_grouped_scan2")
+        return out if keep else out.to_host()
+
+    def scan2_last(self):
+        """(SCAN2_ROUTE_* of the last scan2 / grouped_scan2 call, rows one workgroup of it owns)"""
+        r, t = C.c_uint32(), C.c_uint32()
+        self._chk(self.lib.aqg_scan2_last(self.ctx, C.byref(r), C.byref(t)), "aqg_scan2_last")
         return r.value, t.value
 
     # -- exponential moving averages (ordered scan of affine maps: include/aqg.h, exponential moving averages section)

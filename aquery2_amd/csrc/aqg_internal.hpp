@@ -63,6 +63,7 @@ struct aqg_ctx {
     uint32_t asof_routes = 0, asof_groups = 0, asof_passes = 0;   // aqg_join_asof: routes, distinct build tuples and the ordering step's digit passes of the last call (aqg_join_asof_last)
     uint32_t wj_routes = 0, wj_groups = 0, wj_passes = 0;         // aqg_join_window* / aqg_interval_fold: the same of the last call, plus the fold's route (aqg_join_window_last)
     uint32_t rank_routes = 0, rank_tile = 0;    // aqg_rank*: routes of the last call and the sorted entries one workgroup of its emit kernel owns (aqg_rank_last)
+    uint32_t scan2_route = 0, scan2_tile = 0;   // aqg_scan2*: the route of the last call and the rows one workgroup of it owns (aqg_scan2_last)
     uint32_t winq_tile = 0, winq_halo = 0;      // aqg_window_quantiles*: rows per workgroup and halo rows of the last call (aqg_window_quantiles_last)
     // aqg_rangew*: the packed step counters of the last bounds call (rising steps in the low word, falling in the high one) and the
     // row count of the last fold, from which aqg_rangew_last derives the block tree's geometry

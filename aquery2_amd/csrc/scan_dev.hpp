@@ -261,6 +261,75 @@ __device__ inline void var_short_tile(const T* __restrict__ x, uint32_t n, uint3
     }
 }
 
+// ---- pair statistics (covw / corrw / betaw and their running forms: pair_window.hip) ------------------------------------------------
+// The two columns of a pair call have any two of the ten numeric dtypes, and the kernels are not instantiated per (TX, TY): a row is
+// staged once into an 8-byte SLOT by a wave-uniform switch on the dtype tag, and everything behind the staging load is dtype-blind.
+// Every dtype of up to four bytes and both floating ones convert to double exactly, so their slot is the double and x - k in double IS
+// anchored<T>(x, k); an 8-byte integer keeps its bits and the difference is taken in two's complement, as anchored<T> takes it (`wide`).
+__device__ inline uint64_t slot_of(double v) { return (uint64_t)__double_as_longlong(v); }
+__device__ inline double slot_diff(uint64_t x, uint64_t k, bool wide) {
+    return wide ? (double)(int64_t)(x - k) : __longlong_as_double((long long)x) - __longlong_as_double((long long)k);
+}
+__host__ __device__ inline bool slot_wide(int t) { return t == AQG_INT64 || t == AQG_UINT64; }
+// element i of a column of dtype t as a slot (t is one of the ten numeric tags: the entries check it)
+__device__ inline uint64_t slot_load(const void* __restrict__ p, int t, uint64_t i) {
+    switch (t) {
+    case AQG_INT8: return slot_of((double)static_cast<const int8_t*>(p)[i]);
+    case AQG_INT16: return slot_of((double)static_cast<const int16_t*>(p)[i]);
+    case AQG_INT32: return slot_of((double)static_cast<const int32_t*>(p)[i]);
+    case AQG_UINT8: return slot_of((double)static_cast<const uint8_t*>(p)[i]);
+    case AQG_UINT16: return slot_of((double)static_cast<const uint16_t*>(p)[i]);
+    case AQG_UINT32: return slot_of((double)static_cast<const uint32_t*>(p)[i]);
+    case AQG_FLOAT: return slot_of((double)static_cast<const float*>(p)[i]);
+    default: return static_cast<const uint64_t*>(p)[i];                      // INT64 / UINT64 / DOUBLE: the bits
+    }
+}
+// the statistic of n rows from their sums about ANY pair of constants: FAM 0 cov, 1 corr, 2 beta (population moments).  The co-deviation
+// sums come first, so that the short routes, which hold them directly (sx = sy = 0), and the prefix route share one finish.
+// corr: NaN where either computed variance is not positive, clamped to [-1, 1]; beta: NaN where that of x is not positive.
+template <int FAM> __device__ inline double pair_finish(double cxy, double cxx, double cyy, double n) {
+    if constexpr (FAM == 0) return cxy / n;
+    else if constexpr (FAM == 1) {
+        if (!(cxx > 0 && cyy > 0)) return __builtin_nan("");
+        const double r = cxy / (sqrt(cxx) * sqrt(cyy));
+        return r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);
+    } else return cxx > 0 ? cxy / cxx : __builtin_nan("");
+}
+template <int FAM> __device__ inline double pair_value(double sx, double sy, double sxy, double sxx, double syy, double n) {
+    const double cxy = sxy - sx * sy / n;
+    double cxx = 0, cyy = 0;
+    if constexpr (FAM != 0) cxx = sxx - sx * sx / n;
+    if constexpr (FAM == 1) cyy = syy - sy * sy / n;
+    return pair_finish<FAM>(cxy, cxx, cyy, n);
+}
+constexpr int pair_sums(int fam) { return fam == 0 ? 3 : (fam == 1 ? 5 : 4); }     // cov: sx sy sxy; beta: + sxx; corr: + syy
+template <int NS> struct dsums { double v[NS]; };                                  // {sx, sy, sxy, sxx, syy}, the first NS of them
+// co-moments about a pair of anchors, beside mom_alg: kx, ky = the slots of the range's first row, n = rows, fl = bit 0 / 1: x / y is
+// `wide` (rides in the aggregate so that the combine needs no dtype), and the five sums of (x - kx), (y - ky), their squares and their
+// product.  The combine moves b onto a's anchors with dx = kxb - kxa, dy = kyb - kya:
+//   sum (x - kxa)(y - kya) = sxy_b + dx sy_b + dy sx_b + n_b dx dy,   the squares as in mom_alg;
+// every term is bounded by n_b range_x range_y.  Identity: n = 0.
+struct comom { uint64_t kx, ky; uint32_t n, fl; double sx, sy, sxx, syy, sxy; };
+struct comom_alg {
+    using A = comom;
+    __device__ static A identity() { A r; r.kx = r.ky = 0; r.n = r.fl = 0; r.sx = r.sy = r.sxx = r.syy = r.sxy = 0; return r; }
+    __device__ static A lift(uint64_t x, uint64_t y, uint32_t fl) { A r = identity(); r.kx = x; r.ky = y; r.n = 1; r.fl = fl; return r; }
+    __device__ static A op(A a, A b) {
+        if (!b.n) return a;
+        if (!a.n) return b;
+        const double dx = slot_diff(b.kx, a.kx, b.fl & 1u), dy = slot_diff(b.ky, a.ky, b.fl & 2u), nb = (double)b.n;
+        A r;
+        r.kx = a.kx; r.ky = a.ky; r.fl = a.fl;
+        r.n = a.n + b.n;
+        r.sx = a.sx + (b.sx + nb * dx);
+        r.sy = a.sy + (b.sy + nb * dy);
+        r.sxx = a.sxx + (b.sxx + (2.0 * dx * b.sx + nb * dx * dx));
+        r.syy = a.syy + (b.syy + (2.0 * dy * b.sy + nb * dy * dy));
+        r.sxy = a.sxy + (b.sxy + ((dx * b.sy + dy * b.sx) + nb * dx * dy));
+        return r;
+    }
+};
+
 // K2: exclusive scan of the tile aggregates by one workgroup
 template <class ALG> __global__ void __launch_bounds__(SB) agg_scan_kernel(typename ALG::A* __restrict__ tile_agg, uint32_t ntiles) {
     using A = typename ALG::A;

@@ -88,14 +88,19 @@ template <class ROWS> __device__ inline typename carry_alg<typename ROWS::ALG, R
 
 // ---- the writer ------------------------------------------------------------------------------------------------------------------
 // W_MAXP / W_MINP: running max / min without the reference's seed (maxw / minw, w >= n); W_RAW / W_MOM: the prefix in accumulator form
-// (wide windows); W_RED_*: one result per group, stored where the group ends (the flat layout only)
+// (wide windows); W_CO3 / W_CO5 / W_CO4: the first 3 / 5 / 4 anchored co-moment sums of a pair of columns (wide pair windows: cov / corr /
+// beta), W_COVS / W_CORRS / W_BETAS: the running pair statistics; W_RED_*: one result per group, stored where the group ends (the flat
+// layout only)
 enum : int { W_SUMS = 0, W_AVGS, W_MINS, W_MAXS, W_MAXP, W_MINP, W_VARS, W_STDDEVS, W_RAW, W_MOM, W_DIST, W_GID, W_EMA,
+             W_CO3, W_CO5, W_CO4, W_COVS, W_CORRS, W_BETAS,
              W_RED_SUM, W_RED_AVG, W_RED_MIN, W_RED_MAX, W_RED_VAR, W_RED_STDDEV };
 template <class T, int WR> struct prefix_out {
     using type = std::conditional_t<WR == W_SUMS || WR == W_RED_SUM, std::conditional_t<std::is_floating_point_v<T>, double, aqg_i128>,
                  std::conditional_t<WR == W_AVGS || WR == W_VARS || WR == W_STDDEVS || WR == W_EMA || WR == W_RED_AVG || WR == W_RED_VAR || WR == W_RED_STDDEV, double,
                  std::conditional_t<WR == W_RAW, typename sum_alg<T>::A, std::conditional_t<WR == W_MOM, dpair,
-                 std::conditional_t<WR == W_DIST || WR == W_GID, uint32_t, T>>>>>;
+                 std::conditional_t<WR == W_CO3, dsums<3>, std::conditional_t<WR == W_CO4, dsums<4>, std::conditional_t<WR == W_CO5, dsums<5>,
+                 std::conditional_t<WR == W_COVS || WR == W_CORRS || WR == W_BETAS, double,
+                 std::conditional_t<WR == W_DIST || WR == W_GID, uint32_t, T>>>>>>>>>;
 };
 // a scan that resumes a column sharded by row range (aqg_scan_resume): the sum of every earlier row in the result's LongType
 // and the number of earlier rows.  Kept apart from the tile accumulator, which is 64 bits wide for <= 4-byte integer columns
@@ -148,6 +153,10 @@ __device__ inline typename prefix_out<T, WR>::type emit(const typename ALG::A& r
         }
         return WR == W_RED_STDDEV ? sqrt(d) : d;
     } else if constexpr (WR == W_MOM) return dpair{run.s, run.q};
+    else if constexpr (WR == W_CO3) return dsums<3>{{run.sx, run.sy, run.sxy}};
+    else if constexpr (WR == W_CO4) return dsums<4>{{run.sx, run.sy, run.sxy, run.sxx}};
+    else if constexpr (WR == W_CO5) return dsums<5>{{run.sx, run.sy, run.sxy, run.sxx, run.syy}};
+    else if constexpr (WR == W_COVS || WR == W_CORRS || WR == W_BETAS) return pair_value<WR - W_COVS>(run.sx, run.sy, run.sxy, run.sxx, run.syy, (double)run.n);
     else if constexpr (WR == W_DIST) return pos;
     else if constexpr (WR == W_GID) return gid;
     else return ALG::value(run);                                                   // W_EMA: b, or num / den

@@ -376,6 +376,11 @@ int aqg_grouped_rank(aqg_ctx* ctx, struct aqg_groupby* g, int method, int order,
 int aqg_grouped_rank_flat(aqg_ctx* ctx, struct aqg_groupby* g, int method, int order, uint32_t k, int t, const void* xflat, void* out_flat_dev);
 int aqg_rank_last(aqg_ctx* ctx, uint32_t* routes_host, uint32_t* tile_rows_host);
 
+/* ---- pair windows: moving and running statistics of two columns ------------------
+ * covw / corrw / betaw and the running covs / corrs / betas of two columns, per group and flat: aqg_scan2, aqg_grouped_scan2,
+ * aqg_grouped_scan2_flat, aqg_scan2_last.  Their contract and declarations are a header of their own, part of this one. */
+#include "aqg_pair.h"
+
 /* ---- exponential moving averages ------------------------------------------------
  * The decayed averages beside avgs / avgw: kdb's `ema`, pandas' `ewm(...).mean()`, "decayed price by symbol".  THE REFERENCE HAS NO SUCH
  * FUNCTION (server/aggregations.h stops at the windows): these entries stand in for the host loop per group a user would otherwise

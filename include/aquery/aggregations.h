@@ -157,6 +157,34 @@ template <class T, template <typename...> class VT, class Ret> inline void devic
     dev::check(aqg_rank(rt.ctx(), method, order, k, dev::tag_of<std::remove_cv_t<T>>::value, in.d, n, dout), "aqg_rank");
     if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
 }
+// ret = the pair statistic op (AQG_SCAN2_*) of x and y (include/aqg_pair.h): n doubles.  When both columns are per-group
+// temporaries of the generated loop that are ALL of one group of the same grouping, the call is answered for all groups by one
+// aqg_grouped_scan2_flat (Runtime::vcol_scan2) and `ret` becomes this group's slice of that result; any other pair of vectors goes
+// through aqg_scan2 on its own rows.
+template <class Ret> inline void device_scan2(int op, uint32_t w, const void* x, bool x_borrowed, int xtag, size_t xsz,
+                                              const void* y, bool y_borrowed, int ytag, size_t ysz, uint32_t n, Ret& ret) {
+    using RT = std::remove_cv_t<std::remove_pointer_t<decltype(ret.container)>>;
+    static_assert(std::is_same_v<RT, double>, "covw / corrw / betaw: the result holds doubles");
+    auto& rt = dev::Runtime::get();
+    if (n == 0) return;
+    if (rt.deferred_whole(x, n) && rt.deferred_whole(y, n)) {
+        dev::Entry* ex = rt.deferred_at(x);
+        dev::Entry* ey = rt.deferred_at(y);
+        if (ex->dgroup == ey->dgroup && ex->dg == ey->dg) {
+            dev::GroupCtx* gc = ex->dgroup;
+            const uint32_t g = ex->dg;
+            const int r = rt.vcol_scan2(gc, op, ex->dv, ey->dv, w);
+            rt.defer_slice(ret.container, (size_t)n * sizeof(RT), gc, g, r);
+            if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+            return;
+        }
+    }
+    void* dout = rt.result(ret.container, (size_t)n * sizeof(RT));
+    dev::In ix(x, (size_t)n * xsz, x_borrowed);
+    dev::In iy(y, (size_t)n * ysz, y_borrowed);
+    dev::check(aqg_scan2(rt.ctx(), op, xtag, ix.d, ytag, iy.d, n, w, static_cast<double*>(dout)), "aqg_scan2");
+    if (ret.capacity == 0 && GC::scratch_space == nullptr) rt.touch(ret.container);
+}
 // ret = decay(halflife, t): 2^(-|t[i] - t[i-1]| / halflife), 1 at the first element; a per-group temporary that is all of its group: one
 // aqg_grouped_decay_from_times_flat for all groups (Runtime::vcol_decay)
 template <class T, template <typename...> class VT, class Ret> inline void device_decay(double halflife, const VT<T>& t, Ret& ret) {
@@ -470,6 +498,47 @@ template <class K, class T, template <typename...> class VT, class Ret, std::ena
 void ntile(K k, const VT<T>& arr, Ret& ret, bool desc = false) { aq::device_rank(AQG_RANK_NTILE, desc ? AQG_ORDER_DESC : AQG_ORDER_ASC, (uint32_t)k, arr, ret); }
 template <class K, class T, template <typename...> class VT, std::enable_if_t<aq::is_vt<VT, T> && std::is_integral_v<K>>* = nullptr>
 inline decayed_t<VT, uint32_t> ntile(K k, const VT<T>& arr, bool desc = false) { decayed_t<VT, uint32_t> ret(arr.size); ntile(k, arr, ret, desc); return ret; }
+// covw(w, x, y) / corrw(w, x, y) / betaw(w, x, y): the population covariance, the correlation and the slope of y on x over the last
+// min(w, i + 1) elements; covs(x, y) / corrs(x, y) / betas(x, y): the same over the elements so far -- pandas' rolling(w).cov(ddof=0) /
+// .corr() and expanding().  Doubles; corr and beta are NaN where a variance they divide by is not positive (the first element, constant
+// windows).  The reference's header has none of them (include/aqg_pair.h).  Scalars: one element has no spread.
+#define AQ_PAIR_CALL(op, w)                                                                                       \
+    aq::device_scan2(op, (uint32_t)(w), x.container, x.capacity == 0, aq::dev::tag_of<std::remove_cv_t<TX>>::value, sizeof(TX),   \
+                     y.container, y.capacity == 0, aq::dev::tag_of<std::remove_cv_t<TY>>::value, sizeof(TY), x.size, ret)
+#define AQ_PAIRW(name, op, scalar)                                                                                \
+    template <class W, class TX, template <typename...> class VX, class TY, template <typename...> class VY, class Ret,           \
+              std::enable_if_t<aq::is_vt<VX, TX> && aq::is_vt<VY, TY> && std::is_integral_v<W> && !std::is_arithmetic_v<Ret>>* = nullptr> \
+    void name(W w, const VX<TX>& x, const VY<TY>& y, Ret& ret) {                                                  \
+        if (x.size != y.size) aq::dev::check(AQG_ERR_ARG, #name ": the two columns differ in length");            \
+        if (!(w > 0)) aq::dev::check(AQG_ERR_ARG, #name ": the window must hold a row");                          \
+        AQ_PAIR_CALL(op, w);                                                                                      \
+    }                                                                                                             \
+    template <class W, class TX, template <typename...> class VX, class TY, template <typename...> class VY,      \
+              std::enable_if_t<aq::is_vt<VX, TX> && aq::is_vt<VY, TY> && std::is_integral_v<W>>* = nullptr>       \
+    inline decayed_t<VX, double> name(W w, const VX<TX>& x, const VY<TY>& y) { decayed_t<VX, double> ret(x.size); name(w, x, y, ret); return ret; } \
+    template <class W, class TX, class TY, std::enable_if_t<std::is_integral_v<W> && std::is_arithmetic_v<TX> && std::is_arithmetic_v<TY>>* = nullptr> \
+    constexpr double name(W, const TX&, const TY&) { return scalar; }
+#define AQ_PAIRS(name, op, scalar)                                                                                \
+    template <class TX, template <typename...> class VX, class TY, template <typename...> class VY, class Ret,    \
+              std::enable_if_t<aq::is_vt<VX, TX> && aq::is_vt<VY, TY> && !std::is_arithmetic_v<Ret>>* = nullptr>  \
+    void name(const VX<TX>& x, const VY<TY>& y, Ret& ret) {                                                       \
+        if (x.size != y.size) aq::dev::check(AQG_ERR_ARG, #name ": the two columns differ in length");            \
+        AQ_PAIR_CALL(op, 0);                                                                                      \
+    }                                                                                                             \
+    template <class TX, template <typename...> class VX, class TY, template <typename...> class VY,               \
+              std::enable_if_t<aq::is_vt<VX, TX> && aq::is_vt<VY, TY>>* = nullptr>                                \
+    inline decayed_t<VX, double> name(const VX<TX>& x, const VY<TY>& y) { decayed_t<VX, double> ret(x.size); name(x, y, ret); return ret; } \
+    template <class TX, class TY, std::enable_if_t<std::is_arithmetic_v<TX> && std::is_arithmetic_v<TY>>* = nullptr> \
+    constexpr double name(const TX&, const TY&) { return scalar; }
+AQ_PAIRW(covw, AQG_SCAN2_COVW, 0.0)
+AQ_PAIRW(corrw, AQG_SCAN2_CORRW, std::numeric_limits<double>::quiet_NaN())
+AQ_PAIRW(betaw, AQG_SCAN2_BETAW, std::numeric_limits<double>::quiet_NaN())
+AQ_PAIRS(covs, AQG_SCAN2_COVS, 0.0)
+AQ_PAIRS(corrs, AQG_SCAN2_CORRS, std::numeric_limits<double>::quiet_NaN())
+AQ_PAIRS(betas, AQG_SCAN2_BETAS, std::numeric_limits<double>::quiet_NaN())
+#undef AQ_PAIRW
+#undef AQ_PAIRS
+#undef AQ_PAIR_CALL
 // (decayt is the name generated code can use: under its `using namespace std` a call to `decay` is ambiguous with std::decay)
 #define AQ_DECAY(name)                                                                                            \
     template <class H, class T, template <typename...> class VT, class Ret, std::enable_if_t<aq::is_vt<VT, T> && std::is_arithmetic_v<H>>* = nullptr> \

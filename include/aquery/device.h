@@ -294,6 +294,24 @@ public:
         if (rc != AQG_OK) die("aqg_grouped_rank_flat", rc, ctx_);
         return vcol_new(c, key, r);
     }
+    // the pair statistic op (AQG_SCAN2_*: covw / corrw / betaw over w rows, or the running covs / corrs / betas) of the columns vx, vy of
+    // every group's slice: ONE aqg_grouped_scan2_flat over the two flat columns per (op, vx, vy, w), whatever the number of groups (the
+    // running ops ignore w, which is left out of their key)
+    size_t grouped_scan2_calls = 0;             // aqg_grouped_scan2_flat calls made so far (the tests count them)
+    int vcol_scan2(GroupCtx* c, int op, int vx, int vy, uint32_t w) {
+        const std::array<uint64_t, 6> key{10, (uint64_t)op, (uint64_t)vx, (uint64_t)vy, op >= AQG_SCAN2_COVW ? w : 0u, 0};
+        auto it = c->memo.find(key);
+        if (it != c->memo.end()) return it->second;
+        VCol r; r.layout = 1; r.tag = AQG_DOUBLE;
+        const void* xf = vcol_flat_ptr(c, vx);
+        const void* yf = vcol_flat_ptr(c, vy);
+        int rc = aqg_malloc(ctx(), (size_t)c->n * 8 + 16, &r.dptr);
+        if (rc != AQG_OK) die("aqg_malloc", rc, ctx_);
+        ++grouped_scan2_calls;
+        rc = aqg_grouped_scan2_flat(ctx_, c->handle, op, c->vcols[vx].tag, xf, c->vcols[vy].tag, yf, w, static_cast<double*>(r.dptr));
+        if (rc != AQG_OK) die("aqg_grouped_scan2_flat", rc, ctx_);
+        return vcol_new(c, key, r);
+    }
     // decay(halflife, t) of every group's slice: one aqg_grouped_decay_from_times_flat over the flat column
     int vcol_decay(GroupCtx* c, int v, double halflife) {
         uint64_t hbits;
